@@ -17,6 +17,12 @@ are one workload. `--config 2` is BASELINE configs[1] (1M pages per GPU, 1 % wor
 `--config 3` is configs[2] (16M pages in all, clustered 10 %, strong).
 Synthetic inputs (SPEC §6), resident in HBM before the timed region.
 
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the
+headline with the per-stage times of those steps. `--full` adds everything else the line can
+carry (the box's read / copy ceilings and the roofline, payload bytes, the REPLICA == CURRENT
+check, the CPU baseline, at N > 1 the link timing and the same-run N = 1 reference).
+`--dump-outputs DIR` writes a seeded sample of what the last timed step computed (dump_outputs).
+
 Prints ONE JSON line on rank 0 (contract in the task statement); everything else -> stderr.
 """
 from __future__ import annotations
@@ -56,6 +62,20 @@ def parse():
     ap.add_argument("--mode", choices=["uniform", "clustered"], default=None)
     ap.add_argument("--ppm", type=int, default=None, help="write density in parts per million")
     ap.add_argument("--seed", type=int, default=2026)
+    ap.add_argument("--full", action="store_true",
+                    help="pages workload: beside the headline also measure and check everything "
+                         "else the line can carry: this GPU's read / copy ceilings and the diff "
+                         "kernel's roofline against them, the stream's payload bytes, REPLICA == "
+                         "CURRENT after the timed steps, the CPU baseline (unless --no-cpu) and, "
+                         "at N > 1, the link timing and the same-run N = 1 reference. Off: set "
+                         "up, warm up, time the steps, print the headline with the per-stage "
+                         "times of those steps. (The other --workload lines always carry all "
+                         "their fields.)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="pages workload: after the timed steps rank 0 writes what the last step "
+                         "left a caller as DIR/<name>.npy (float32 / float64): a fixed, seeded "
+                         "sample of REPLICA's pages and, at N = 1, of the diff stream's records "
+                         "beside the stream's size (dump_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--overlap", choices=["auto", "on", "off"], default="auto",
@@ -1000,6 +1020,51 @@ def run_nw(args):
     barrier(world)
 
 
+DUMP_PAGES = 1024  # pages sampled by --dump-outputs: 16 MiB of REPLICA as float32
+
+
+def dump_outputs(out_dir: str, ctx, n: int, runs=None) -> None:
+    """--dump-outputs: what the last timed step left a caller, as <name>.npy under out_dir. The
+    pages are a fixed, seeded sample (every page when the shard has at most DUMP_PAGES; the first
+    and the last page always), the same for every run with the same page count:
+      sample_page_ids   float64[K]        the sampled local page indices, ascending
+      replica_pages     float32[K, 4096]  REPLICA's bytes of those pages (after the apply)
+    and, with the step's diff stream `runs` (N = 1):
+      diff_total_bytes  float64[1]        the stream's size, rec_off[n] (SPEC §3)
+      diff_record_bytes float64[K]        each sampled page's record size
+      diff_records      float32[sum]      the bytes of those records, in page order"""
+    import gallocy_amd as ga
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    if n <= DUMP_PAGES:
+        ids = np.arange(n, dtype=np.int64)
+    else:
+        ids = np.random.default_rng(0).choice(n, DUMP_PAGES, replace=False)
+        ids = np.unique(np.concatenate([ids, [0, n - 1]]).astype(np.int64))
+    np.save(out / "sample_page_ids.npy", ids.astype(np.float64))
+    pages = np.stack([ctx.download("replica", int(p), 1)[0] for p in ids])
+    np.save(out / "replica_pages.npy", pages.astype(np.float32))
+    if runs is None:
+        return
+    total = runs.total()
+    ro = np.empty(n + 1, np.uint64)
+    d2h = ga.gdsm.lib().gdsm_memcpy_d2h
+    ga.gdsm.check(d2h(ctx.handle, ro.ctypes.data, runs.s.rec_off, ro.nbytes), "d2h")
+    if int(ro[n]) != total or (ro[ids + 1] < ro[ids]).any() or (ro[ids + 1] > total).any():
+        raise RuntimeError("--dump-outputs: the stream's rec_off is not a prefix sum up to its total")
+    sizes = (ro[ids + 1] - ro[ids]).astype(np.int64)
+    recs = np.empty(int(sizes.sum()), np.uint8)
+    at = 0
+    for p, sz in zip(ids, sizes):
+        if sz:
+            ga.gdsm.check(d2h(ctx.handle, recs.ctypes.data + at, runs.s.data + int(ro[p]), int(sz)),
+                          "d2h")
+            at += int(sz)
+    np.save(out / "diff_total_bytes.npy", np.array([total], np.float64))
+    np.save(out / "diff_record_bytes.npy", sizes.astype(np.float64))
+    np.save(out / "diff_records.npy", recs.astype(np.float32))
+
+
 def launch_ranks(args):
     """`bench.py --gpus N` without a launcher: this GPU-free parent starts the N ranks itself
     (torch.distributed.run on 127.0.0.1, one process per GPU), before anything touches a GPU,
@@ -1086,12 +1151,14 @@ def main():
         # Two diff streams: release k+1 may be diffed while release k is applied
         runs = [ga.Runs(ctx, n, cap=n * cap_pp) for _ in range(2)]
 
-    # this box's read and copy ceilings over the shard's own arenas (REPLICA is the copy's
-    # destination, then generated again)
-    box = box_ceilings(ctx, n, read=(ctx.arena_ptr("twin"), ctx.arena_ptr("current")),
-                       copy=(ctx.arena_ptr("current"), ctx.arena_ptr("replica")))
-    ctx.gen_pages(seed=args.seed, mode=mode, ppm=ppm, first_global=rank * n, stride=1,
-                  arenas=("replica",))
+    # --full: this box's read and copy ceilings over the shard's own arenas (REPLICA is the
+    # copy's destination, then generated again)
+    box = {}
+    if args.full:
+        box = box_ceilings(ctx, n, read=(ctx.arena_ptr("twin"), ctx.arena_ptr("current")),
+                           copy=(ctx.arena_ptr("current"), ctx.arena_ptr("replica")))
+        ctx.gen_pages(seed=args.seed, mode=mode, ppm=ppm, first_global=rank * n, stride=1,
+                      arenas=("replica",))
 
     def steps(k: int, pipelined: bool):
         if shard is not None:
@@ -1120,20 +1187,22 @@ def main():
             shard.calibrate()
         steps(max(0, args.warmup - 1), pipelined)
         total = sum(r.total() for d, r in enumerate(shard.send[0]) if shard.counts[d])
-        host = None
         pay = 0
         for d, r in enumerate(shard.send[0]):
-            if shard.counts[d]:
+            if args.full and shard.counts[d]:
                 h = r.to_host()
                 pay += payload_bytes(h.rec_off, h.data)
     else:
         steps(args.warmup, pipelined)
-        total = runs[0].total()  # raises ENOSPC if the capacity was too small
+        # (raises ENOSPC if the capacity was too small; nothing was diffed with --warmup 0)
+        total = runs[0].total() if args.warmup else None
         assert not pipelined or args.warmup < 2 or runs[1].total() == total
-        host = runs[0].to_host()
-        pay = payload_bytes(host.rec_off, host.data)
+        pay = 0
+        if args.full and args.warmup:
+            host = runs[0].to_host()
+            pay = payload_bytes(host.rec_off, host.data)
+            del host
     drain()
-    del host
 
     def barrier():
         if world > 1:
@@ -1168,12 +1237,21 @@ def main():
     watchdog(args, rank, world, "timed releases")
     dt_other = timed(not pipelined, False)[0] if args.compare_overlap else None
     dt, prof = timed(pipelined, True)
+    if total is None:  # --warmup 0: the sizes come from the timed steps' stream
+        total = runs[0].total()
+        if args.full:
+            host = runs[0].to_host()
+            pay = payload_bytes(host.rec_off, host.data)
+            del host
+    if args.dump_outputs and rank == 0:
+        last = None if shard is not None else runs[(args.steps - 1) % 2] if pipelined else runs[0]
+        dump_outputs(args.dump_outputs, ctx, n, last)
     watchdog(args, rank, world, "link timing")
     # The xGMI link alone: the same releases again (untimed for `value`) with GDSM_XCHG_TIMED, a
     # device-side barrier before each transfer, so the exchange stage starts once every rank's
     # streams are ready and times the RCCL group, not the wait for the peers' diffs.
     link = None
-    if shard is not None and shard.comm is not None:
+    if args.full and shard is not None and shard.comm is not None:
         shard.flags |= exchange.XCHG_TIMED
         try:
             _, plink = timed(pipelined, True)
@@ -1187,7 +1265,9 @@ def main():
 
     # correctness of the measured work: REPLICA == CURRENT afterwards (diff of the two is empty)
     watchdog(args, rank, world, "verification and the stats all-reduces")
-    if shard is None:
+    if not args.full:
+        replica_ok = None
+    elif shard is None:
         chk = ga.Runs(ctx, n, cap=1 << 20)
         ws = ctx.buffer(ga.gdsm.lib().gdsm_diff_workspace_bytes(n))
         rc = ga.gdsm.lib().gdsm_diff_raw(ctx.arena_ptr("replica"), ctx.arena_ptr("current"), None,
@@ -1213,7 +1293,7 @@ def main():
     step_bytes = n * 8192 + (1 if fused else 2) * total + pay
     ms_step = dt / args.steps * 1e3
     value = world * n * args.steps / dt
-    traffic, traffic_src = read_traffic(n, mode_name, ppm, fused)
+    traffic, traffic_src = read_traffic(n, mode_name, ppm, fused) if args.full else (None, None)
 
     # per-stage time per step, max over ranks (HIP events on the stream each stage runs on)
     stage_ms = {k: prof[k][0] / args.steps for k in ("diff", "exchange", "apply")}
@@ -1242,7 +1322,8 @@ def main():
                         "stage, which includes waiting for the peers' diffs. peak: 7 links x 153 "
                         "GB/s (all of an MI355X's xGMI); peak_links_used: the N-1 links one "
                         "rank's peers use"}
-    ref_ms, ref_src = efficiency_ref(world * n, mode_name, ppm) if world > 1 else (None, None)
+    ref_ms, ref_src = (efficiency_ref(world * n, mode_name, ppm) if args.full and world > 1
+                       else (None, None))
     exch = None if shard is None else {
         "transport": shard.transport, "fixed_budgets": bool(shard.flags),
         "comm_ranks": shard.comm.size()[0] if shard.comm is not None else None,
@@ -1250,7 +1331,7 @@ def main():
         "sent_remote_bytes_per_step": shard.sent_remote,
         "received_bytes_per_step": shard.received}
     same = None
-    if world > 1 and args.same_run_ref == "on":
+    if args.full and world > 1 and args.same_run_ref == "on":
         # the N-rank run's arenas and communicator go first, then rank 0 alone runs the N = 1
         # step of the same total workload (the other ranks wait at the barrier)
         watchdog(args, rank, world, "teardown of the N-rank run")
@@ -1302,6 +1383,7 @@ def main():
             "step_hbm_gbs": round(step_bytes * args.steps / dt / 1e9, 1),
             "pipelined": pipelined,
             "fused_apply": fused,
+            "full": args.full,
             ("serial_ms_per_step" if pipelined else "pipelined_ms_per_step"):
                 None if dt_other is None else round(dt_other / args.steps * 1e3, 4),
             "roofline": with_box({"bound": "hbm", "kernel": DIFF_KERNEL,
@@ -1310,8 +1392,8 @@ def main():
                                   "traffic": traffic, "traffic_source": traffic_src,
                                   "algorithmic_bytes_per_launch": int(diff_bytes),
                                   "avg_launch_ms": round(avg_diff_ms, 4)}, box, "read"),
-            "step_frac_of_box_read": round(step_bytes * args.steps / dt / 1e9
-                                           / box["box_read_gbs"], 4),
+            **({"step_frac_of_box_read": round(step_bytes * args.steps / dt / 1e9
+                                               / box["box_read_gbs"], 4)} if box else {}),
             "stages": stages,
             "stage_ms_per_step": {k: round(v, 4) for k, v in stage_ms.items()},
             "exchange": exch,
@@ -1323,7 +1405,14 @@ def main():
             "replica_equals_current": bool(replica_ok),
             "cpu_baseline": None,
         }
-        if not args.no_cpu and world == 1:  # the host baseline is a 1-GPU figure (rank 0, N = 1)
+        if not args.full:
+            # the fields that --full measures or checks (or that rest on them) are left out
+            for k in ("step_hbm_gbs", "roofline", "efficiency_ref_ms", "efficiency_ref_source",
+                      "efficiency_same_run", "same_run_reference", "replica_equals_current",
+                      "cpu_baseline"):
+                res.pop(k, None)
+            del res["config"]["payload_bytes_per_step"]
+        elif not args.no_cpu and world == 1:  # the host baseline is a 1-GPU figure (rank 0, N = 1)
             res["cpu_baseline"] = cpu_baseline(mode, ppm, args.seed, args.cpu_seconds)
         print(json.dumps(res), flush=True)
     watchdog(args, rank, world, "teardown")

@@ -17,8 +17,8 @@ if [ -n "${DEV_K:-}" ]; then
   step tests 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -k "$DEV_K"
 fi
 if [ -n "${DEV_BENCH:-1}" ]; then
-  step bench_fused 300 python -u bench.py --steps 20 --warmup 3 --no-cpu --fuse on
-  step bench_unfused 300 python -u bench.py --steps 20 --warmup 3 --no-cpu --fuse off
+  step bench_fused 300 python -u bench.py --steps 20 --warmup 3 --full --no-cpu --fuse on
+  step bench_unfused 300 python -u bench.py --steps 20 --warmup 3 --full --no-cpu --fuse off
 fi
 if [ -n "${DEV_PMC:-}" ]; then
   COH_PMC_VARIANTS=0 bash scripts/dev/coh_pmc.sh > $OUT/cohpmc.log 2>&1; echo "cohpmc rc=$?"; tail -4 $OUT/cohpmc.log

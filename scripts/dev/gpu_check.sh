@@ -21,7 +21,7 @@ if [ "$WHAT" = all ] || [ "$WHAT" = tests ]; then
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = bench ]; then
-  step bench 600 python bench.py --steps 20 --warmup 3
+  step bench 600 python bench.py --steps 20 --warmup 3 --full
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = prof ]; then
   step rocprof 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --steps 20 --warmup 3 --no-cpu

@@ -11,9 +11,9 @@ if [ "$W" = all ] || [ "$W" = tests ]; then
      "smoke|200|python -c 'import __graft_entry__ as g; g.smoke()'" || exit $?
 fi
 if [ "$W" = all ] || [ "$W" = bench ]; then
-  $S "bench_northstar|300|python -u bench.py" \
-     "bench_config2|300|python -u bench.py --config 2 --no-cpu" \
-     "bench_config3|300|python -u bench.py --config 3" \
+  $S "bench_northstar|300|python -u bench.py --full" \
+     "bench_config2|300|python -u bench.py --config 2 --full --no-cpu" \
+     "bench_config3|300|python -u bench.py --config 3 --full" \
      "bench_twin|300|python -u bench.py --workload twin --steps 10 --warmup 2" \
      "bench_coh_uniform|300|python -u bench.py --workload coherence --dist uniform --steps 5 --warmup 2" \
      "bench_coh_zipf|300|python -u bench.py --workload coherence --dist zipf --steps 5 --warmup 2" \

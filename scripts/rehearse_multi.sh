@@ -13,7 +13,7 @@ for spec in "2 on" "2 off" "4 on"; do
   echo "=== $name"
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $1 \
     --master-addr 127.0.0.1 --master-port $port bench.py --gpus $1 --steps 5 --warmup 1 \
-    --pages 262144 --no-cpu --overlap $2 > $OUT/$name.log 2>&1
+    --pages 262144 --full --no-cpu --overlap $2 > $OUT/$name.log 2>&1
   rc=$?
   echo "=== $name rc=$rc"; grep '^{' $OUT/$name.log | cut -c1-400 || tail -n 20 $OUT/$name.log
   if [ $rc -ne 0 ]; then exit $rc; fi

@@ -36,9 +36,9 @@ if [ "$WHAT" = all ] || [ "$WHAT" = tests ]; then
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = bench ]; then
-  step bench 600 python -u bench.py
-  step bench_config3_n1 600 python -u bench.py --config 3
-  step bench_config2 600 python -u bench.py --config 2 --no-cpu
+  step bench 600 python -u bench.py --full
+  step bench_config3_n1 600 python -u bench.py --config 3 --full
+  step bench_config2 600 python -u bench.py --config 2 --full --no-cpu
   step bench_mmult 300 python -u bench.py --workload mmult
   step bench_twin 300 python -u bench.py --workload twin --steps 10 --warmup 2
 fi

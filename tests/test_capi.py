@@ -129,7 +129,18 @@ def test_legacy_caller_on_gallocy_internal_heap():
     gdsm_set_allocator, replays the three test/test_diff.cpp bodies through libgdsm's diff()
     symbol, checks every output lies in the internal heap's zone, and frees it with
     internal_free (gallocy/utils/diff.cpp:135-136, allocators/internal.cpp:31-57)."""
-    r = subprocess.run([str(CALLER)], capture_output=True, text=True, timeout=120)
+    import os
+
+    from gallocy_amd import _lib
+    # the library the other tests load (gallocy_amd/lib, or GDSM_LIB) comes first in the caller's
+    # search, before the run path it was linked with
+    libdir = str(_lib.LIB_PATH.parent)
+    env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(
+        [libdir] + [p for p in os.environ.get("LD_LIBRARY_PATH", "").split(os.pathsep) if p]))
+    r = subprocess.run([str(CALLER)], capture_output=True, text=True, timeout=120, env=env)
+    if r.returncode == 127:  # the loader's own failure: say what it searched
+        ldd = subprocess.run(["ldd", str(CALLER)], capture_output=True, text=True, env=env)
+        r.stderr += f"\n{_lib.LIB_PATH} exists: {_lib.LIB_PATH.exists()}\n{ldd.stdout}{ldd.stderr}"
     assert r.returncode == 0, r.stderr
     assert r.stdout.startswith("ok ")
 

@@ -100,8 +100,8 @@ def test_bench_multi_rank_rehearsal_gloo(ranks, overlap):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            f"--nproc-per-node={ranks}", "--master-addr", "127.0.0.1", "--master-port",
            str(_port()), str(root / "bench.py"), "--gpus", str(ranks), "--steps", "3",
-           "--warmup", "1", "--total-pages", str(ranks * ranks * 8192), "--no-cpu", "--overlap",
-           overlap]
+           "--warmup", "1", "--total-pages", str(ranks * ranks * 8192), "--full", "--no-cpu",
+           "--overlap", overlap]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=100)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -141,7 +141,7 @@ def test_bench_gpus_2_without_launcher():
     parent spawns the two ranks itself, and rank 0's line reports n_gpus 2 (ranks share cuda:0
     over the gloo rehearsal transport here; RCCL on a multi-GPU node)."""
     d = _bench_no_launcher(["--gpus", "2", "--steps", "2", "--warmup", "1", "--total-pages",
-                            str(4 * 8192), "--no-cpu"])
+                            str(4 * 8192), "--full", "--no-cpu"])
     assert d["n_gpus"] == 2 and d["replica_equals_current"] is True
     assert d["config"]["total_pages"] == 4 * 8192 and d["config"]["pages_per_gpu"] == 2 * 8192
 
