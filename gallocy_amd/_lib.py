@@ -62,7 +62,6 @@ SIGNATURES = {
     "gdsm_prof_enable": (C.c_int, [vp, C.c_int]),
     "gdsm_prof_read": (C.c_int, [vp, C.POINTER(C.c_double), u64p]),
     "gdsm_rounds": (C.c_int, [vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "gdsm_rounds": (C.c_int, [vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gdsm_probe_ceiling": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_uint64, C.c_int,
                                      C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "gdsm_gen_pages": (C.c_int, [vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int,
@@ -86,6 +85,12 @@ SIGNATURES = {
                                       C.c_uint64, vp]),
     "gdsm_apply_raw": (C.c_int, [vp, vp, C.c_uint64, vp, vp, vp, vp]),
     "gdsm_twin_raw": (C.c_int, [vp, vp, vp, C.c_uint64, vp]),
+    "gdsm_merge": (C.c_int, [vp, C.c_uint32, C.POINTER(GdsmRuns), C.POINTER(vp), vp, C.c_uint64,
+                             C.POINTER(GdsmRuns), vp, vp]),
+    "gdsm_merge_workspace_bytes": (C.c_uint64, [C.c_uint64]),
+    "gdsm_merge_raw": (C.c_int, [C.c_uint32, C.POINTER(vp), C.POINTER(vp), u64p, C.POINTER(vp),
+                                 u64p, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp, vp,
+                                 C.c_uint64, vp]),
     "gdsm_coh_init": (C.c_int, [vp, C.c_uint32]),
     "gdsm_coherence_batch": (C.c_int, [vp, vp, C.c_uint64, u64p]),
     "gdsm_coherence_batch_async": (C.c_int, [vp, vp, C.c_uint64, vp]),

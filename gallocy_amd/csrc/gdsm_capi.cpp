@@ -269,6 +269,7 @@ int gdsm_fini(gdsm_ctx* ctx) {
   if (ctx->nw_ws) (void)hipFree(ctx->nw_ws);
   if (ctx->nw_stage) (void)hipFree(ctx->nw_stage);
   if (ctx->wire_ws) (void)hipFree(ctx->wire_ws);
+  if (ctx->merge_ws) (void)hipFree(ctx->merge_ws);
   for (auto* p : ctx->ids_safe)
     if (p) (void)hipFree(p);
   for (auto& kv : ctx->runs_busy) (void)hipEventDestroy(kv.second);
@@ -797,6 +798,81 @@ int gdsm_apply_raw(uint8_t* target, const uint32_t* ids, uint64_t n, const uint6
     err = sink;
   }
   GDSM_TRY(gdsm::launch_apply(target, ids, n, rec_off, data, err,
+                              static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+// ---- merge (SPEC §8) ------------------------------------------------------------------------
+// The argument rules gdsm_merge and gdsm_merge_raw share, checked before anything is enqueued;
+// fills the launcher's view of the inputs.
+static int merge_args(uint32_t K, const uint64_t* const* rec_off, const uint8_t* const* data,
+                      const uint64_t* caps, const uint32_t* const* in_ids, const uint64_t* in_n,
+                      const uint32_t* out_ids, uint64_t n_out, const uint64_t* out_rec_off,
+                      const uint8_t* out_data, uint64_t out_cap, gdsm::MergeIn* m) {
+  if (K == 0 || K > GDSM_MAX_NODES || !rec_off || !data || !caps || !in_n) return -EINVAL;
+  if (!out_rec_off || (!out_data && out_cap)) return -EINVAL;
+  if (n_out > 0xFFFFFFFFull) return -EINVAL;  // page lists are u32
+  m->K = K;
+  for (uint32_t k = 0; k < K; ++k) {
+    const uint32_t* ids = in_ids ? in_ids[k] : nullptr;
+    if (!rec_off[k] || (!data[k] && caps[k])) return -EINVAL;
+    if (!ids && in_n[k] != n_out) return -EINVAL;  // record i is out entry i
+    if (ids && !out_ids) return -EINVAL;           // the identity out list joins nothing
+    if (rec_off[k] == out_rec_off || (out_data && data[k] == out_data)) return -EINVAL;
+    m->rec_off[k] = rec_off[k];
+    m->data[k] = data[k];
+    m->ids[k] = ids;
+    m->n[k] = in_n[k];
+    m->cap[k] = caps[k];
+  }
+  return 0;
+}
+
+uint64_t gdsm_merge_workspace_bytes(uint64_t n_out) { return gdsm::merge_workspace_bytes(n_out); }
+
+int gdsm_merge(gdsm_ctx* ctx, uint32_t K, const gdsm_runs* in, const uint32_t* const* in_ids,
+               const uint32_t* out_ids, uint64_t n_out, gdsm_runs* out, uint32_t* conflicts,
+               uint64_t* stats) {
+  if (!ctx || !in || !out || K == 0 || K > GDSM_MAX_NODES) return -EINVAL;
+  if (out->n_cap ? n_out > out->n_cap : (out->owned && n_out > out->n)) return -EINVAL;
+  const uint64_t* ro[GDSM_MAX_NODES];
+  const uint8_t* data[GDSM_MAX_NODES];
+  uint64_t caps[GDSM_MAX_NODES], ns[GDSM_MAX_NODES];
+  for (uint32_t k = 0; k < K; ++k) {
+    ro[k] = in[k].rec_off;
+    data[k] = in[k].data;
+    caps[k] = in[k].cap;
+    ns[k] = in[k].n;
+  }
+  gdsm::MergeIn m{};
+  int rc = merge_args(K, ro, data, caps, in_ids, ns, out_ids, n_out, out->rec_off, out->data,
+                      out->cap, &m);
+  if (rc) return rc;
+  CtxGuard g(ctx);
+  if (g.rc) return g.rc;
+  auto busy = ctx->runs_busy.find(out->rec_off);  // an async apply still reading the out stream
+  if (busy != ctx->runs_busy.end()) GDSM_TRY(hipStreamWaitEvent(ctx->stream, busy->second, 0));
+  rc = ensure(ctx, &ctx->merge_ws, &ctx->merge_ws_bytes, gdsm::merge_workspace_bytes(n_out));
+  if (rc) return rc;
+  out->n = n_out;
+  GDSM_TRY(gdsm::launch_merge(m, out_ids, n_out, out->rec_off, out->data, out->cap, conflicts,
+                              stats, ctx->err, ctx->merge_ws, ctx->merge_ws_bytes, ctx->stream,
+                              ctx->P()));
+  return 0;
+}
+
+int gdsm_merge_raw(uint32_t K, const uint64_t* const* rec_off, const uint8_t* const* data,
+                   const uint64_t* caps, const uint32_t* const* in_ids, const uint64_t* in_n,
+                   const uint32_t* out_ids, uint64_t n_out, uint64_t* out_rec_off,
+                   uint8_t* out_data, uint64_t out_cap, uint32_t* conflicts, uint64_t* stats,
+                   uint32_t* err, void* workspace, uint64_t workspace_bytes, void* stream) {
+  gdsm::MergeIn m{};
+  int rc = merge_args(K, rec_off, data, caps, in_ids, in_n, out_ids, n_out, out_rec_off, out_data,
+                      out_cap, &m);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < gdsm::merge_workspace_bytes(n_out)) return -EINVAL;
+  GDSM_TRY(gdsm::launch_merge(m, out_ids, n_out, out_rec_off, out_data, out_cap, conflicts, stats,
+                              err, static_cast<uint8_t*>(workspace), workspace_bytes,
                               static_cast<hipStream_t>(stream)));
   return 0;
 }

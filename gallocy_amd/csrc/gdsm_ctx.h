@@ -59,6 +59,9 @@ struct gdsm_ctx {
   uint8_t* wire_ws = nullptr;
   uint64_t wire_ws_bytes = 0;
   uint64_t wire_hdr[4] = {};  // host staging of the frame header
+  // gdsm_merge: the fatal word, record sizes and their scan
+  uint8_t* merge_ws = nullptr;
+  uint64_t merge_ws_bytes = 0;
   // checked copies of caller page-id lists (launch_check_ids): one per stream, so an async
   // apply's list is never overwritten by a call on the main stream
   // [2]: the target-page list of gdsm_diff_apply_ids (main stream, beside [0])

@@ -96,6 +96,25 @@ hipError_t launch_diff_split(const uint8_t* twin, const uint8_t* cur, DiffSplit 
 hipError_t launch_apply(uint8_t* target, const uint32_t* ids, uint64_t n,
                         const uint64_t* rec_off, const uint8_t* data, uint32_t* err,
                         hipStream_t s, Prof* prof = nullptr);
+// gdsm_merge (SPEC §8; gdsm_merge.hip): K <= 8 input streams in priority order, each with its
+// offsets, data, capacity, record count and page list (NULL: record i is out entry i).
+struct MergeIn {
+  const uint64_t* rec_off[8];
+  const uint8_t* data[8];
+  const uint32_t* ids[8];
+  uint64_t n[8];
+  uint64_t cap[8];
+  uint32_t K;
+};
+uint64_t merge_workspace_bytes(uint64_t n_out);
+// The merged stream of out entries out_ids[0..n_out) (NULL: the identity) into out_rec_off[n_out+1]
+// / out_data[out_cap]; conflicts (n_out x u32) and stats (2 x u64) may be NULL. err |= 1 for a
+// malformed record (it contributes nothing), 16 / 8 for malformed offsets / an unsorted page list
+// (the output is then empty). Five launches and two small memsets on s, no host synchronisation.
+hipError_t launch_merge(const MergeIn& in, const uint32_t* out_ids, uint64_t n_out,
+                        uint64_t* out_rec_off, uint8_t* out_data, uint64_t out_cap,
+                        uint32_t* conflicts, uint64_t* stats, uint32_t* err, uint8_t* ws,
+                        uint64_t ws_bytes, hipStream_t s, Prof* prof = nullptr);
 // A stream about to be applied by gdsm_exchange: checked whole (offsets from 0, non-decreasing,
 // 4-aligned, rec_off[n] <= budget; page indices < n_pages, copied to safe[n]). A rejected stream
 // has every offset zeroed (nothing applied); err |= 16 (malformed offsets), 32 (over budget),

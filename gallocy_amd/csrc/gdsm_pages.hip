@@ -13,6 +13,7 @@
 // No wave waits for a ticket that a wave not yet running holds.
 #include "gdsm_common.h"
 #include "gdsm_launch.h"
+#include "gdsm_record.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -1134,23 +1135,7 @@ __device__ __forceinline__ void store_run_chunk(uint8_t* __restrict__ page, uint
 // search over the row's pair offsets — so short and long runs cost the same per byte. `has` is
 // false for rows without a record. Returns false in the lanes of a row whose record is malformed.
 // kMode: 0 = plain stores, 1 = MEASUREMENT ONLY (no replica stores), 2 = nontemporal stores.
-template <uint32_t kW>
-__device__ __forceinline__ uint32_t grp_incl_sum(uint32_t x) {
-  return kW == 16 ? row_incl_sum(x) : wave_incl_sum(x);
-}
-template <uint32_t kW>
-__device__ __forceinline__ uint32_t grp_incl_max(uint32_t x) {
-  return kW == 16 ? row_incl_max(x) : wave_incl_max(x);
-}
-template <uint32_t kW>
-__device__ __forceinline__ uint32_t grp_last(uint32_t x) {
-  return kW == 16 ? row_last(x) : lane_bcast(x, 63);
-}
-template <uint32_t kW>
-__device__ __forceinline__ uint32_t grp_prev(uint32_t x) {
-  return kW == 16 ? row_prev(x) : from_prev_lane(x);
-}
-
+// (pass 1's header loop is record_runs_check of gdsm_record.h, which the merge kernels share)
 template <int kMode, typename P32, typename P8, uint32_t kW = 16>
 __device__ __forceinline__ bool apply_rows(uint8_t* __restrict__ page, P32 rec32, P8 rec8,
                                            uint32_t size, bool has, uint32_t& sink) {
@@ -1159,21 +1144,7 @@ __device__ __forceinline__ bool apply_rows(uint8_t* __restrict__ page, P32 rec32
   uint32_t nr = has ? rec32[0] : 0u;
   bool bad = has && (nr == 0 || nr > kMaxRuns || size < 4u + 4u * nr);
   if (bad) nr = 0;
-  const uint32_t nit = lane_bcast(wave_incl_max((nr + kW - 1) / kW), 63);
-  uint32_t pay = 0, prev_end = 0, lbad = 0;
-  for (uint32_t it = 0; it < nit; ++it) {
-    const uint32_t r = it * kW + lr;
-    const bool v = r < nr;
-    const uint32_t h = v ? rec32[1 + r] : 0u;
-    const uint32_t off = h & 0xFFFFu, len = h >> 16, end = v ? off + len : 0u;
-    uint32_t pe = grp_prev<kW>(end);
-    if (lr == 0) pe = prev_end;
-    if (v && (len == 0 || end > kPage || off < pe)) lbad = 1;
-    pay += grp_last<kW>(grp_incl_sum<kW>(v ? len : 0u));
-    prev_end = grp_last<kW>(end);
-  }
-  if (grp_last<kW>(grp_incl_max<kW>(lbad))) bad = true;
-  if (has && !bad && size != 4u + 4u * nr + ((pay + 3u) & ~3u)) bad = true;
+  bad = record_runs_check<kW>(rec32, size, has, nr, bad);
   const uint32_t nrw = bad ? 0u : nr;  // runs this row writes
   const uint32_t nit2 = lane_bcast(wave_incl_max((nrw + kW - 1) / kW), 63);
   uint32_t pcarry = 0;

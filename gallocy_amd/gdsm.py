@@ -146,6 +146,37 @@ class Runs:
             check(lib().gdsm_runs_free(self.ctx.handle, C.byref(self.s)), "gdsm_runs_free")
 
 
+class MergeResult:
+    """What Context.merge returns: `runs` (the merged stream), `out_ids` (the DeviceBuffer of its
+    pages, None for the identity), `stats` and `conflicts` (lazy reads that synchronise)."""
+
+    def __init__(self, ctx, runs, out_ids, stats, conflicts, n_out, own):
+        self.ctx, self.runs, self.out_ids, self.n_out = ctx, runs, out_ids, n_out
+        self._stats, self._conflicts, self._own = stats, conflicts, own
+
+    @property
+    def stats(self) -> dict:
+        """{"overlap_bytes", "conflict_bytes"} over all out pages (synchronises)."""
+        self.ctx.sync()
+        s = self._stats.download(np.uint64, 2)
+        return {"overlap_bytes": int(s[0]), "conflict_bytes": int(s[1])}
+
+    @property
+    def conflicts(self) -> Optional[np.ndarray]:
+        """Conflicting bytes per out page (uint32[n_out]; None without want_conflicts)."""
+        if self._conflicts is None:
+            return None
+        self.ctx.sync()
+        return self._conflicts.download(np.uint32, max(self.n_out, 1))[:self.n_out]
+
+    def free(self):
+        """Frees the counters and the page lists merge() uploaded (out_ids included when it was
+        uploaded there), not `runs`."""
+        for b in (self._stats, self._conflicts, *self._own):
+            if b is not None and b.ptr:
+                b.free()
+
+
 class Graph:
     """An instantiated HIP graph of recorded libgdsm calls (Context.capture_end)."""
 
@@ -221,7 +252,7 @@ class Context:
         return Graph(g.value)
 
     PROF_STAGES = ("diff", "apply", "twin", "coh_fold", "coh_reduce", "nw_fill", "nw_trace",
-                   "exchange", "route", "exchange_wait")
+                   "exchange", "route", "exchange_wait", "merge")
 
     def prof_enable(self, on: bool = True):
         check(lib().gdsm_prof_enable(self.handle, int(on)), "gdsm_prof_enable")
@@ -322,6 +353,51 @@ class Context:
         """gdsm_apply_async: the apply overlaps the diffs enqueued after it (double buffering)."""
         check(lib().gdsm_apply_async(self.handle, _ARENA[target], self._ptr(ids), C.byref(runs.s)),
               "gdsm_apply_async")
+
+    def merge(self, streams: Sequence[Runs], ids=None, out_ids=None, out: Optional[Runs] = None,
+              cap: int = 0, want_conflicts: bool = False) -> "MergeResult":
+        """gdsm_merge (docs/SPEC.md §8): `streams` (Runs, in priority order: a later one wins)
+        composed into one stream with the overlapped and conflicting bytes counted. ids: per stream
+        a DeviceBuffer or numpy array of its records' pages (ascending), or None (record i is out
+        entry i). out_ids: the out pages (DeviceBuffer or numpy array, ascending; None with no
+        lists = the identity); with numpy lists and out_ids None the sorted union is computed here
+        and uploaded, device lists need out_ids. Asynchronous; MergeResult.stats synchronises."""
+        K = len(streams)
+        ids = [None] * K if ids is None else list(ids)
+        if len(ids) != K:
+            raise ValueError("one page list (or None) per stream")
+        own = []  # device lists uploaded here
+
+        def dev(a):
+            if a is None or isinstance(a, DeviceBuffer):
+                return a
+            b = self.ids(np.asarray(a))
+            own.append(b)
+            return b
+
+        if out_ids is None and any(i is not None for i in ids):
+            if any(isinstance(i, DeviceBuffer) for i in ids):
+                raise ValueError("device page lists need out_ids")
+            if any(i is None for i in ids):
+                raise ValueError("a stream without a page list needs out_ids")
+            out_ids = np.unique(np.concatenate([np.asarray(i, np.uint32) for i in ids]))
+        if out_ids is None:
+            n_out = streams[0].n if K else 0
+        elif isinstance(out_ids, DeviceBuffer):
+            n_out = out_ids.nbytes // 4
+        else:
+            out_ids = np.ascontiguousarray(out_ids, np.uint32)
+            n_out = len(out_ids)
+        d_out = dev(out_ids)
+        d_ids = [dev(i) for i in ids]
+        out = out or Runs(self, max(n_out, 1), cap)
+        stats = self.buffer(16)
+        conflicts = self.buffer(4 * max(n_out, 1)) if want_conflicts else None
+        arr = (GdsmRuns * max(K, 1))(*[s.s for s in streams])
+        idp = (C.c_void_p * max(K, 1))(*[self._ptr(i) for i in d_ids])
+        check(lib().gdsm_merge(self.handle, K, arr, idp, self._ptr(d_out), n_out, C.byref(out.s),
+                               self._ptr(conflicts), stats.ptr), "gdsm_merge")
+        return MergeResult(self, out, d_out, stats, conflicts, n_out, own)
 
     def _count(self, ids, n):
         if n is not None:

@@ -70,6 +70,7 @@ enum gdsm_prof_stage {
   GDSM_PROF_EXCHANGE,   /* gdsm_exchange: the transfer of the record streams (RCCL group) */
   GDSM_PROF_ROUTE,      /* gdsm_route_events / gdsm_coherence_notify: the transfers */
   GDSM_PROF_EXCHANGE_WAIT, /* gdsm_exchange: the transfer plus the wait for the peers' streams */
+  GDSM_PROF_MERGE,      /* gdsm_merge: its check, size, scan and emit launches together */
   GDSM_PROF_STAGES
 };
 
@@ -179,30 +180,6 @@ int gdsm_rounds(gdsm_ctx* data, gdsm_ctx* pt, uint32_t n_rounds, const uint64_t*
                 const uint32_t* home, const int64_t* id_off, const uint64_t* desc,
                 const int64_t* desc_off, gdsm_runs* runs);
 
-/* ---- DSM rounds on the device ------------------------------------------------------------
- * n_rounds release rounds of one DSM run, each: a coherence batch of fault events on `pt`'s page
- * table (as gdsm_coherence_batch_async, totals row r = totals + 10 r), the application's writes
- * of the round on `data` (copy descriptors as gdsm_memcpy_batch) and the release of the pages
- * written (as gdsm_release with GDSM_RELEASE_RETWIN: diff of list entries ids, applied to
- * REPLICA at home, TWIN := CURRENT), round after round. Instead of three calls per round, ONE
- * persistent launch per context: the page-table rounds on pt's stream, the page-data rounds on
- * data's stream, a device-wide barrier between rounds where the launches had their boundaries.
- * Round r = events [ev_off[r], ev_off[r+1]), list entries [id_off[r], id_off[r+1]) of ids / home,
- * descriptors [desc_off[r], desc_off[r+1]) of desc (3 u64 each). The offset arrays are HOST
- * arrays of n_rounds + 1 entries from 0 (copied to the device by the call); events, totals, ids,
- * home, desc are device pointers. A round's writes are laid onto its released pages by the
- * release itself (no separate copy step), so they must be 8-B aligned (dst, src and bytes) and lie
- * inside the pages that round releases, each page listed once per round; otherwise gdsm_sync on
- * data reports -EINVAL. Limits: <= 2048 pages and <= 2^20 events per round, runs sized for the
- * largest round; data and pt distinct contexts of one device. runs ends holding the last round's
- * stream. Asynchronous on both streams; gdsm_sync on each reports failures (-ETIMEDOUT: a device
- * barrier gave up, never expected). Replaces gallocy_amd/native/replay.cpp's per-round
- * calls for config 5 (test/test_mmult.cpp:51-64's rounds). */
-int gdsm_rounds(gdsm_ctx* data, gdsm_ctx* pt, uint32_t n_rounds, const uint64_t* events,
-                const int64_t* ev_off, uint64_t* totals, const uint32_t* ids,
-                const uint32_t* home, const int64_t* id_off, const uint64_t* desc,
-                const int64_t* desc_off, gdsm_runs* runs);
-
 /* ---- synthetic inputs (SPEC §6) ------------------------------------------------------- */
 /* Fills the arenas named in `arenas` (bit 1<<GDSM_TWIN | 1<<GDSM_CURRENT | 1<<GDSM_REPLICA,
  * 0 = all) for every page; arena page i has global id first_global + i * stride (stride 0 = 1).
@@ -264,6 +241,37 @@ int gdsm_apply(gdsm_ctx* ctx, int target, const uint32_t* ids, const gdsm_runs* 
  * Malformed records are reported by the next gdsm_sync. */
 int gdsm_apply_async(gdsm_ctx* ctx, int target, const uint32_t* ids, const gdsm_runs* in);
 
+/* ---- merge: the diff streams of several writers as one (docs/SPEC.md §8) -------------------
+ * The multiple-writer step at a home (no reference counterpart: resources/NUTSHELL.md:59-69
+ * describes one writer per page): K streams in[0..K), 1 <= K <= GDSM_MAX_NODES, in priority order
+ * (in[k] is "applied after" in[k-1]) become the one stream `out` that gdsm_apply applies with the
+ * same result, restricted to the out pages; where two writers covered the same byte is counted.
+ *   in_ids[k]  (device, in[k].n entries, strictly ascending) the pages of stream k's records;
+ *              NULL (or in_ids itself NULL): record i is out entry i, and in[k].n == n_out;
+ *   out_ids    (device, n_out entries, strictly ascending) the pages of the out records; a stream
+ *              contributes the record whose id equals the page, pages not listed here are ignored
+ *              (pass the union for everything); NULL = the identity, every in_ids[k] NULL too.
+ * Per out page the record's runs are the MAXIMAL ranges of the positions any stream covers (runs
+ * that abut fuse), each byte from the highest k covering it; with K = 1 and a canonical input the
+ * output equals the input byte for byte, and merging is associative byte for byte.
+ *   conflicts  (device, n_out x u32, may be NULL) per out page, the positions covered by at least
+ *              two streams that do not all carry the same byte there;
+ *   stats      (device, 2 x u64, may be NULL) {overlapped bytes (covered by >= 2 streams),
+ *              conflicting bytes} over all out pages.
+ * Capacity as gdsm_diff: rec_off is written in full, data only below out->cap (in whole dwords),
+ * gdsm_runs_total reports -ENOSPC. A record gdsm_apply would refuse contributes nothing (the out
+ * record is built from the other streams) and the next gdsm_sync reports -EINVAL; input offsets
+ * that do not start at 0, decrease, are not 4-aligned or end past the stream's cap, or a page list
+ * that is not strictly ascending, are found before any record is read: the out stream is then
+ * empty (every offset 0, no data written) and the next gdsm_sync reports -EINVAL.
+ * Asynchronous on the context stream, no host synchronisation; sets out->n = n_out. Immediate
+ * -EINVAL: K == 0 or > 8, a NULL ctx / in / out, n_out > out->n_cap, out sharing data or rec_off
+ * with an input, in_ids[k] == NULL with in[k].n != n_out, a list with out_ids == NULL. -EBUSY on
+ * a recording context whose merge workspace would have to grow (merge once before recording). */
+int gdsm_merge(gdsm_ctx* ctx, uint32_t K, const gdsm_runs* in, const uint32_t* const* in_ids,
+               const uint32_t* out_ids, uint64_t n_out, gdsm_runs* out, uint32_t* conflicts,
+               uint64_t* stats);
+
 /* ---- raw entry points (caller-owned device memory, e.g. tensors; stream = hipStream_t) ---- */
 uint64_t gdsm_diff_workspace_bytes(uint64_t n);
 int gdsm_diff_raw(const uint8_t* twin, const uint8_t* cur, const uint32_t* ids, uint64_t n,
@@ -277,6 +285,16 @@ int gdsm_apply_raw(uint8_t* target, const uint32_t* ids, uint64_t n, const uint6
                    const uint8_t* data, uint32_t* err, void* stream);
 int gdsm_twin_raw(uint8_t* twin, const uint8_t* cur, const uint32_t* ids, uint64_t n,
                   void* stream);
+/* gdsm_merge on caller-owned buffers: K arrays of offsets, data, capacities, page lists (in_ids or
+ * an entry NULL as above) and record counts; err as gdsm_apply_raw's (OR-ed with 1 for a malformed
+ * record, 16 / 8 for malformed offsets / an unsorted list; NULL: not reported); workspace of
+ * gdsm_merge_workspace_bytes(n_out) device bytes, its contents need not be kept. */
+uint64_t gdsm_merge_workspace_bytes(uint64_t n_out);
+int gdsm_merge_raw(uint32_t K, const uint64_t* const* rec_off, const uint8_t* const* data,
+                   const uint64_t* caps, const uint32_t* const* in_ids, const uint64_t* in_n,
+                   const uint32_t* out_ids, uint64_t n_out, uint64_t* out_rec_off,
+                   uint8_t* out_data, uint64_t out_cap, uint32_t* conflicts, uint64_t* stats,
+                   uint32_t* err, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* ---- batched coherence (SPEC §5) ------------------------------------------------------- */
 /* Allocates and initialises the page table (state + faults) for n_nodes <= 8; -EINVAL for a
