@@ -270,6 +270,7 @@ int gdsm_fini(gdsm_ctx* ctx) {
   if (ctx->nw_stage) (void)hipFree(ctx->nw_stage);
   if (ctx->wire_ws) (void)hipFree(ctx->wire_ws);
   if (ctx->merge_ws) (void)hipFree(ctx->merge_ws);
+  if (ctx->fetch_ws) (void)hipFree(ctx->fetch_ws);
   for (auto* p : ctx->ids_safe)
     if (p) (void)hipFree(p);
   for (auto& kv : ctx->runs_busy) (void)hipEventDestroy(kv.second);

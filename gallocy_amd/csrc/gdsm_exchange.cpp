@@ -306,6 +306,14 @@ struct gdsm_comm {
   uint64_t blk_off_bytes = 0;
   uint8_t* staging = nullptr;    // this home's notices, destination-major
   uint64_t staging_bytes = 0;
+  // page fetch (gdsm_fetch): [G] requested per home, [G] requests received, [G+1] bounds, flag
+  // word; pinned mirror (words of its own: a notify's last launch may still read rcnt_dev)
+  uint64_t* fcnt_dev = nullptr;
+  uint64_t* fcnt_host = nullptr;
+  uint8_t* fetch_serve = nullptr;  // home: the pages served to other ranks, then their ids (u32)
+  uint64_t fetch_serve_bytes = 0;
+  uint8_t* fetch_recv = nullptr;   // requester: the pages asked of other ranks
+  uint64_t fetch_recv_bytes = 0;
 };
 
 using namespace gdsm::detail;
@@ -318,6 +326,8 @@ int comm_alloc(gdsm_comm* c) {
       hipHostMalloc(reinterpret_cast<void**>(&c->cnt_host), words * 8) != hipSuccess ||
       hipMalloc(reinterpret_cast<void**>(&c->rcnt_dev), words * 8) != hipSuccess ||
       hipHostMalloc(reinterpret_cast<void**>(&c->rcnt_host), words * 8) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&c->fcnt_dev), words * 8) != hipSuccess ||
+      hipHostMalloc(reinterpret_cast<void**>(&c->fcnt_host), words * 8) != hipSuccess ||
       hipMalloc(reinterpret_cast<void**>(&c->verdict), 4 * (size_t)c->nranks) != hipSuccess)
     return -ENOMEM;
   return 0;
@@ -430,7 +440,10 @@ int gdsm_comm_fini(gdsm_comm* c) {
   if (c->ids_chk) (void)hipFree(c->ids_chk);
   if (c->rcnt_dev) (void)hipFree(c->rcnt_dev);
   if (c->rcnt_host) (void)hipHostFree(c->rcnt_host);
-  for (uint8_t* p : {c->route_buf, c->pre, c->blk, c->blk_off, c->staging})
+  if (c->fcnt_dev) (void)hipFree(c->fcnt_dev);
+  if (c->fcnt_host) (void)hipHostFree(c->fcnt_host);
+  for (uint8_t* p : {c->route_buf, c->pre, c->blk, c->blk_off, c->staging, c->fetch_serve,
+                     c->fetch_recv})
     if (p) (void)hipFree(p);
   delete c;
   return 0;
@@ -772,6 +785,134 @@ int gdsm_coherence_notify(gdsm_ctx* ctx, gdsm_comm* c, const uint64_t* batch, ui
                             hipMemcpyDeviceToDevice, s));
   *n_notices = off[G];
   return 0;
+}
+
+// ---- page fetch (SPEC §9) ------------------------------------------------------------------
+// Collective like the two calls above: the split's failure and the staging growths are folded into
+// the one agreement that precedes the transfers. After it, a launch error on this rank is kept
+// until both transfer groups have run (the peers are already committed to them) and returned then.
+int gdsm_fetch(gdsm_ctx* ctx, gdsm_comm* c, const uint32_t* pages, const uint32_t* dst_ids,
+               uint64_t n, uint64_t total_pages, int src, uint32_t dst_arenas) {
+  if (!ctx || !c || (n && !pages)) return -EINVAL;
+  constexpr uint32_t kCur = 1u << GDSM_CURRENT, kTwin = 1u << GDSM_TWIN;
+  if (dst_arenas == 0) dst_arenas = kCur | kTwin;
+  if (src < 0 || src > 2 || (dst_arenas & ~(kCur | kTwin)) || ((dst_arenas >> src) & 1u))
+    return -EINVAL;
+  if (!ctx->arena[src] || ((dst_arenas & kCur) && !ctx->arena[GDSM_CURRENT]) ||
+      ((dst_arenas & kTwin) && !ctx->arena[GDSM_TWIN]))
+    return -EINVAL;
+  if (c->device != ctx->device || c->nranks > (int)gdsm::kFetchMaxRanks || total_pages == 0 ||
+      total_pages > GDSM_MAX_COH_PAGES)
+    return -EINVAL;
+  if (recording(ctx)) return -EBUSY;  // the call reads the counts back on the host
+  const int G = c->nranks, me = c->rank;
+  Transport* xp = c->xp;
+  CtxGuard g(ctx);
+  if (g.rc) return g.rc;
+  hipStream_t s = ctx->stream;
+  const uint64_t per = (total_pages + G - 1) / G;
+  const uint64_t base = (uint64_t)me * per < total_pages ? (uint64_t)me * per : total_pages;
+  const uint64_t end = ((uint64_t)me + 1) * per < total_pages ? ((uint64_t)me + 1) * per : total_pages;
+  const uint64_t block = end - base;  // this home's pages (none when total_pages < nranks)
+  uint64_t* cnt = c->fcnt_dev;  // [0,G) requested, [G,2G) received, [2G,3G+1) bounds, [4G] flag
+  uint32_t* flag = reinterpret_cast<uint32_t*>(cnt + 4 * G);
+  int local = 0;
+  {
+    hipError_t e = hipMemsetAsync(flag, 0, 8, s);
+    if (e == hipSuccess)
+      e = gdsm::launch_fetch_split(pages, dst_ids, n, total_pages, per, (uint32_t)G, ctx->n_pages,
+                                   cnt, cnt + 2 * G, flag, s);
+    if (e != hipSuccess) {  // ask for nothing; the agreement below refuses everywhere
+      local = map_err(e);
+      (void)hipMemsetAsync(cnt, 0, 8 * (4 * (size_t)G + 1), s);
+    }
+  }
+  int rc = xp->all_to_all_u64(cnt, cnt + G, 1, s);
+  if (rc) return rc;
+  uint64_t* h = c->fcnt_host;
+  GDSM_TRY(hipMemcpyAsync(h, cnt, 8 * (4 * (size_t)G + 1), hipMemcpyDeviceToHost, s));
+  GDSM_TRY(hipStreamSynchronize(s));
+  // off: where each requester's slice sits in the home's staging; roff: where each home's pages
+  // land in the requester's (the own slice takes no room in either)
+  std::vector<uint64_t> off(G + 1, 0), roff(G + 1, 0);
+  for (int p = 0; p < G; ++p) {
+    off[p + 1] = off[p] + (p == me ? 0 : h[G + p]);
+    roff[p + 1] = roff[p] + (p == me ? 0 : h[p]);
+  }
+  const uint64_t served = off[G], remote = roff[G];
+  const uint64_t kPg = GDSM_PAGE_SZ;
+  if (!local)
+    local = ensure(ctx, &c->fetch_serve, &c->fetch_serve_bytes, served ? served * (kPg + 4) : 1);
+  if (!local) local = ensure(ctx, &c->fetch_recv, &c->fetch_recv_bytes, remote ? remote * kPg : 1);
+  // every rank agrees before anything moves: 4 = some rank failed, 2 = some rank's list is invalid
+  // or some home's context is smaller than its block
+  const bool invalid = (reinterpret_cast<uint32_t*>(h + 4 * G)[0] & 1u) || block > ctx->n_pages;
+  uint64_t verdict = (local ? kVerdictLocal : 0u) | (invalid ? 2u : 0u);
+  rc = xp->agree_max(&verdict, s);
+  if (rc) return rc;
+  if (verdict & kVerdictLocal) return refused(local);
+  if (verdict & 2) return -EINVAL;
+
+  const bool both = dst_arenas == (kCur | kTwin);
+  uint8_t* a0 = ctx->arena[(dst_arenas & kCur) ? GDSM_CURRENT : GDSM_TWIN];
+  uint8_t* a1 = both ? ctx->arena[GDSM_TWIN] : nullptr;
+  uint32_t* req = reinterpret_cast<uint32_t*>(c->fetch_serve + served * kPg);
+  int late = 0;  // a launch error of this rank once the peers are committed to the transfers
+  gdsm::ProfScope ps(ctx->P(), GDSM_PROF_FETCH, s);
+  // pages homed here: arena to arena
+  late = map_err(gdsm::launch_fetch_local(ctx->arena[src], pages, dst_ids, h[2 * G + me], h[me],
+                                          base, block, ctx->n_pages, a0, a1, ctx->err, s));
+  // the request slices to the homes
+  rc = xp->group_start();
+  for (int p = 0; p < G && !rc; ++p) {
+    if (p == me) continue;
+    if (h[p]) rc = xp->send(pages + h[2 * G + p], 4 * h[p], p, s);
+    if (!rc && h[G + p]) rc = xp->recv(req + off[p], 4 * h[G + p], p, s);
+  }
+  int rc2 = xp->group_end(s);
+  if (rc || rc2) return rc ? rc : rc2;
+  {
+    const int e = map_err(gdsm::launch_fetch_gather(ctx->arena[src], req, served, base, block,
+                                                    c->fetch_serve, ctx->err, s));
+    if (!late) late = e;
+  }
+  // the pages back to the requesters
+  rc = xp->group_start();
+  for (int p = 0; p < G && !rc; ++p) {
+    if (p == me) continue;
+    if (h[G + p]) rc = xp->send(c->fetch_serve + off[p] * kPg, kPg * h[G + p], p, s);
+    if (!rc && h[p]) rc = xp->recv(c->fetch_recv + roff[p] * kPg, kPg * h[p], p, s);
+  }
+  rc2 = xp->group_end(s);
+  if (rc || rc2) return rc ? rc : rc2;
+  if (late) return late;
+  GDSM_TRY(gdsm::launch_fetch_scatter(c->fetch_recv, pages, dst_ids, h[2 * G + me], h[me], remote,
+                                      ctx->n_pages, a0, a1, ctx->err, s));
+  return 0;
+}
+
+int gdsm_notices_fetch_list(gdsm_ctx* ctx, const uint64_t* notices, uint64_t n, uint32_t want,
+                            uint32_t* pages_out, uint64_t cap, uint64_t* n_out) {
+  if (!ctx || !n_out || (n && !notices) || (cap && !pages_out) || want == 0 || want > 3 ||
+      n > GDSM_MAX_COH_PAGES)
+    return -EINVAL;
+  if (recording(ctx)) return -EBUSY;
+  CtxGuard g(ctx);
+  if (g.rc) return g.rc;
+  hipStream_t s = ctx->stream;
+  const uint64_t nb = gdsm::fetch_list_blocks(n), nb1 = nb ? nb : 1;
+  // block offsets (u64), the total (u64), block counts (u32)
+  int rc = ensure(ctx, &ctx->fetch_ws, &ctx->fetch_ws_bytes, 12 * nb1 + 8);
+  if (rc) return rc;
+  uint64_t* blk_off = reinterpret_cast<uint64_t*>(ctx->fetch_ws);
+  uint64_t* total = blk_off + nb1;
+  uint32_t* blk = reinterpret_cast<uint32_t*>(total + 1);
+  GDSM_TRY(gdsm::launch_fetch_list(notices, n, want, blk, blk_off, total, pages_out, cap, s));
+  uint64_t got = 0;
+  GDSM_TRY(hipMemcpyAsync(&got, total, 8, hipMemcpyDeviceToHost, s));
+  GDSM_TRY(hipStreamSynchronize(s));
+  *n_out = got;
+  return got > cap ? -ENOSPC : 0;
 }
 
 }  // extern "C"

@@ -194,6 +194,35 @@ hipError_t launch_notice_emit(const uint64_t* pt, uint64_t n_pages, const uint64
                               const uint64_t* blk_off, const uint64_t* dest_base, uint64_t* out,
                               hipStream_t s);
 
+// Page fetch (SPEC §9; gdsm_fetch.hip).
+constexpr uint32_t kFetchMaxRanks = 255;  // the split finds every home's slice in one workgroup
+// A rank's request list: validation (bad |= 1: not strictly ascending, a page >= total_pages, a
+// destination >= n_pages), per-home bounds[G+1] and counts[G] (u64; they always sum to n).
+hipError_t launch_fetch_split(const uint32_t* pages, const uint32_t* dst_ids, uint64_t n,
+                              uint64_t total_pages, uint64_t per, uint32_t G, uint64_t n_pages,
+                              uint64_t* counts, uint64_t* bounds, uint32_t* bad, hipStream_t s);
+// Home: staging[j] := page req[j] - base of src for the n received requests; an id outside
+// [base, base + block) copies nothing (err |= 8).
+hipError_t launch_fetch_gather(const uint8_t* src, const uint32_t* req, uint64_t n, uint64_t base,
+                               uint64_t block, uint8_t* staging, uint32_t* err, hipStream_t s);
+// Requester: the cnt list entries outside [skip_at, skip_at + skip), in order, from staging pages
+// 0 .. cnt - 1 into a0 / a1 (a1 may be NULL) at dst_ids[i] (NULL: pages[i]).
+hipError_t launch_fetch_scatter(const uint8_t* staging, const uint32_t* pages,
+                                const uint32_t* dst_ids, uint64_t skip_at, uint64_t skip,
+                                uint64_t cnt, uint64_t n_pages, uint8_t* a0, uint8_t* a1,
+                                uint32_t* err, hipStream_t s);
+// Requester and home at once: list entries [first, first + cnt) from src page pages[i] - base.
+hipError_t launch_fetch_local(const uint8_t* src, const uint32_t* pages, const uint32_t* dst_ids,
+                              uint64_t first, uint64_t cnt, uint64_t base, uint64_t block,
+                              uint64_t n_pages, uint8_t* a0, uint8_t* a1, uint32_t* err,
+                              hipStream_t s);
+// Notices -> fetch list: blk (u32) and blk_off (u64) hold fetch_list_blocks(n) entries each;
+// *total = the wanted notices, of which the first cap pages are written to out.
+uint64_t fetch_list_blocks(uint64_t n);
+hipError_t launch_fetch_list(const uint64_t* notices, uint64_t n, uint32_t want, uint32_t* blk,
+                             uint64_t* blk_off, uint64_t* total, uint32_t* out, uint64_t cap,
+                             hipStream_t s);
+
 // GPU NW alignment (legacy diff()): workspace per pair and the fill + trace launches.
 uint64_t nw_pair_ws_bytes(uint32_t max_len);
 hipError_t launch_nw(const uint8_t* a, const uint64_t* a_off, const uint8_t* b,

@@ -446,3 +446,28 @@ def coherence_notify(ctx: gdsm.Context, comm: Comm, batch: int, n: int, base: in
     check(gdsm.lib().gdsm_coherence_notify(ctx.handle, comm.handle, batch, n, base, totals,
                                            notices, cap, C.byref(nn)), "gdsm_coherence_notify")
     return nn.value
+
+
+def notices_fetch_list(ctx: gdsm.Context, notices: int, n: int, want: int, out: int,
+                       cap: int) -> int:
+    """gdsm_notices_fetch_list (SPEC §9): of this node's n notices (device pointer), the pages it
+    gained with no access before, for reading (want bit 0) and/or for writing (bit 1), ascending
+    into `out` (device, cap u32); returns how many. ctx may be the page-table context."""
+    k = C.c_uint64(0)
+    check(gdsm.lib().gdsm_notices_fetch_list(ctx.handle, notices, n, want, out, cap, C.byref(k)),
+          "gdsm_notices_fetch_list")
+    return k.value
+
+
+def fetch(ctx: gdsm.Context, comm: Comm, pages, dst_ids, n: int, total_pages: int,
+          src=gdsm.REPLICA, dst=("current", "twin")):
+    """gdsm_fetch (SPEC §9; collective): the home copies (arena `src` at rank page // per) of the
+    n global pages listed at `pages` (device, strictly ascending) into this rank's arenas `dst` at
+    dst_ids (device; None: at the page ids themselves). Contents always come from the home, not
+    from the page table's owner. Enqueued on ctx's stream; sync before reading the arenas."""
+    mask = 0
+    for a in dst:
+        mask |= 1 << gdsm._ARENA[a]
+    check(gdsm.lib().gdsm_fetch(ctx.handle, comm.handle, gdsm.Context._ptr(pages),
+                                gdsm.Context._ptr(dst_ids), n, total_pages, gdsm._ARENA[src],
+                                mask), "gdsm_fetch")

@@ -71,6 +71,7 @@ enum gdsm_prof_stage {
   GDSM_PROF_ROUTE,      /* gdsm_route_events / gdsm_coherence_notify: the transfers */
   GDSM_PROF_EXCHANGE_WAIT, /* gdsm_exchange: the transfer plus the wait for the peers' streams */
   GDSM_PROF_MERGE,      /* gdsm_merge: its check, size, scan and emit launches together */
+  GDSM_PROF_FETCH,      /* gdsm_fetch: its two transfer groups and the gather / scatter launches */
   GDSM_PROF_STAGES
 };
 
@@ -507,6 +508,64 @@ int gdsm_route_events(gdsm_ctx* ctx, gdsm_comm* comm, const uint64_t* events, ui
 int gdsm_coherence_notify(gdsm_ctx* ctx, gdsm_comm* comm, const uint64_t* batch, uint64_t n,
                           uint64_t base, uint64_t* totals_dev, uint64_t* notices, uint64_t cap,
                           uint64_t* n_notices);
+
+/* ---- page fetch: contents from the home copies to the nodes (docs/SPEC.md §9) ---------------
+ * The other direction of a home-based DSM. gdsm_diff / gdsm_exchange / gdsm_merge take a writer's
+ * changes to the page's home copy (REPLICA at the home rank); gdsm_fetch takes a page's contents
+ * from its home to a node that gained access to it: the "copy over the latest contents" step of
+ * resources/NUTSHELL.md:61-69, which the reference only describes (its transport would be
+ * gallocy/http/client.cpp:39-91). Contents ALWAYS come from the home copy, rank p / per with per =
+ * ceil(total_pages / nranks) as in §5b above: the page table's `owner` names the last writer, not
+ * the holder of the data, and the last writer's release (gdsm_exchange) is what brings the home
+ * copy up to date.
+ *
+ * Collective: every rank of `comm` calls it, also a rank that wants nothing (n = 0).
+ *   pages      device, n GLOBAL page ids, strictly ascending, each < total_pages
+ *              (total_pages <= GDSM_MAX_COH_PAGES);
+ *   dst_ids    device, n entries: where entry i lands in THIS rank's arenas (NULL: at pages[i]);
+ *              every destination < gdsm_n_pages(ctx); the destinations of one call must be
+ *              distinct (with duplicates, which entry's contents stay is unspecified);
+ *   src        the arena the homes serve from, normally GDSM_REPLICA; page p is page p - home * per
+ *              of its home's arena, and a home's context must hold at least its block,
+ *              min(total_pages, (r+1) * per) - min(total_pages, r * per) pages (possibly none);
+ *   dst_arenas bit 1<<GDSM_CURRENT and/or 1<<GDSM_TWIN, 0 = both; src may not be one of them.
+ * Effect: for every entry i and every arena named, arena[dst(i)] := the home copy of pages[i],
+ * byte for byte. With both arenas the page arrives clean (TWIN == CURRENT: its next diff is
+ * empty). No other page of any arena changes on any rank; src is only read. Pages homed at the
+ * calling rank are copied arena to arena on the device: no staging buffer, no transfer.
+ *
+ * Runs on the context's main stream after everything enqueued on it and after pending
+ * gdsm_exchange / gdsm_apply_async work (no gdsm_sync needed in between). It synchronises the host
+ * (one read of the per-home counts), so on a recording context it fails with -EBUSY; the page
+ * moves themselves are still being written on ctx's stream when it returns.
+ *
+ * Memory: the call stages whole pages in buffers the communicator keeps (they only grow): at a home
+ * 4 KiB + 4 B per page it serves to OTHER ranks in this call, at a requester 4 KiB per page it asks
+ * of OTHER ranks. A fetch is not chunked: size the lists accordingly.
+ *
+ * Refusals are collective, before anything moves: every rank returns -EINVAL if any rank's list is
+ * not strictly ascending or names a page >= total_pages or a destination >= its n_pages, or if any
+ * home's context is smaller than its block. A rank whose own step fails (staging it cannot
+ * allocate, a launch error) returns that error and every other rank -ECANCELED, together.
+ * Immediate -EINVAL (the same on every rank by construction): NULL ctx or comm, n without pages,
+ * a bad src or dst_arenas, an arena the context lacks, total_pages 0 or over the limit, more than
+ * 255 ranks, a comm on another device. A request id a home receives that is outside its block
+ * (only a corrupted transfer can produce one) copies nothing and the home's next gdsm_sync reports
+ * -EINVAL. With profiling on, GDSM_PROF_FETCH times the transfers and the page moves. */
+int gdsm_fetch(gdsm_ctx* ctx, gdsm_comm* comm, const uint32_t* pages, const uint32_t* dst_ids,
+               uint64_t n, uint64_t total_pages, int src, uint32_t dst_arenas);
+/* From notices to a fetch list. Filters this node's n notices (device, as gdsm_coherence_notify
+ * wrote them: sorted by page, at most one per page): keeps those whose access before is 0 and
+ * whose access after `want` selects (bit 0: gained for reading, 0 -> 1; bit 1: gained for writing,
+ * 0 -> 2) and writes their global pages to pages_out (device, cap entries) in order, so the list
+ * is strictly ascending, ready for gdsm_fetch. An upgrade 1 -> 2 needs no contents and is never
+ * listed. Synchronises and sets *n_out; -ENOSPC, with *n_out = the count needed, when cap is too
+ * small (the first cap pages are written). ctx may be the page-table context that received the
+ * notices: the list is a plain device array that the data context's gdsm_fetch then reads.
+ * -EINVAL for a NULL ctx or n_out, n without notices, cap without pages_out, want outside 1..3,
+ * n > GDSM_MAX_COH_PAGES; -EBUSY on a recording context. */
+int gdsm_notices_fetch_list(gdsm_ctx* ctx, const uint64_t* notices, uint64_t n, uint32_t want,
+                            uint32_t* pages_out, uint64_t cap, uint64_t* n_out);
 
 const char* gdsm_version(void);
 /* Process-wide kernel-variant knobs for measurement (every value produces the same results):
