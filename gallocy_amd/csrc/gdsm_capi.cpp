@@ -963,6 +963,9 @@ int gdsm_rounds(gdsm_ctx* data, gdsm_ctx* pt, uint32_t n_rounds, const uint64_t*
   // a round's pages: one look-back granule each; its events: the streaming fold's spans
   if (max_ids > gdsm::kDiffChainUnits || max_ev > (1u << 20)) return -EINVAL;
   if (runs->n_cap ? max_ids > runs->n_cap : (runs->owned && max_ids > runs->n)) return -EINVAL;
+  // every round's stream must fit: a middle round that overflowed cap would leave its pages dirty
+  // (release_page_wg stores only records that end inside cap) with nothing left to report it
+  if (runs->cap < max_ids * (uint64_t)GDSM_MAX_RECORD) return -EINVAL;
   if (n_rounds == 0) return 0;
   if (recording(data) || recording(pt)) return -EBUSY;  // (epochs per launch: not replayable)
   CtxGuard gd(data);

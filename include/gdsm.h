@@ -171,9 +171,14 @@ int gdsm_probe_ceiling(gdsm_ctx* ctx, int kind, const void* a, const void* b, vo
  * home, desc are device pointers. A round's writes are laid onto its released pages by the
  * release itself (no separate copy step), so they must be 8-B aligned (dst, src and bytes) and lie
  * inside the pages that round releases, each page listed once per round; otherwise gdsm_sync on
- * data reports -EINVAL. Limits: <= 2048 pages and <= 2^20 events per round, runs sized for the
- * largest round; data and pt distinct contexts of one device. runs ends holding the last round's
- * stream. Asynchronous on both streams; gdsm_sync on each reports failures (-ETIMEDOUT: a device
+ * data reports -EINVAL. One round's descriptors must not overlap each other (a word two of them
+ * cover is also reported as -EINVAL by gdsm_sync). A descriptor's source must not lie in data's
+ * arenas or in any memory written during the call (runs' buffers, totals): the sources are read
+ * with no ordering against the call's own stores, and this is NOT checked. Limits: <= 2048 pages
+ * and <= 2^20 events per round; runs sized for the largest round, in records (n_cap) and in bytes:
+ * runs->cap >= (pages of the largest round) * GDSM_MAX_RECORD, else -EINVAL from the call before
+ * anything runs (a round whose stream overflowed cap would leave its pages dirty unreported); data
+ * and pt distinct contexts of one device. runs ends holding the last round's stream. Asynchronous on both streams; gdsm_sync on each reports failures (-ETIMEDOUT: a device
  * barrier gave up, never expected). Replaces gallocy_amd/native/replay.cpp's per-round
  * calls for config 5 (test/test_mmult.cpp:51-64's rounds). */
 int gdsm_rounds(gdsm_ctx* data, gdsm_ctx* pt, uint32_t n_rounds, const uint64_t* events,
