@@ -125,6 +125,10 @@ SIGNATURES = {
                                         u64p]),
     "gdsm_fetch": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32]),
     "gdsm_notices_fetch_list": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p]),
+    "gdsm_digest": (C.c_int, [vp, C.c_int, vp, C.c_uint64, vp]),
+    "gdsm_digest_raw": (C.c_int, [vp, vp, C.c_uint64, vp, vp]),
+    "gdsm_fetch_changed": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32,
+                                     vp, vp]),
     "gdsm_exchange": (C.c_int, [vp, vp, C.POINTER(GdsmRuns), C.POINTER(vp), C.POINTER(GdsmRuns),
                                 C.POINTER(vp), C.c_int, C.c_uint32]),
 }

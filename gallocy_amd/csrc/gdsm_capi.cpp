@@ -885,6 +885,25 @@ int gdsm_twin_raw(uint8_t* twin, const uint8_t* cur, const uint32_t* ids, uint64
   return 0;
 }
 
+// ---- page digest (SPEC §10) --------------------------------------------------------------
+int gdsm_digest(gdsm_ctx* ctx, int which, const uint32_t* ids, uint64_t n, uint64_t* out) {
+  if (!ctx || which < 0 || which > 2 || !ctx->arena[which] || (n && !out)) return -EINVAL;
+  if (n == 0) return 0;
+  CtxGuard g(ctx);
+  if (g.rc) return g.rc;
+  GDSM_TRY(gdsm::launch_digest(ctx->arena[which], ids, n, ctx->n_pages, out, ctx->err,
+                               ctx->stream, ctx->P()));
+  return 0;
+}
+
+int gdsm_digest_raw(const uint8_t* arena, const uint32_t* ids, uint64_t n, uint64_t* out,
+                    void* stream) {
+  if (!arena || (n && !out)) return -EINVAL;
+  GDSM_TRY(gdsm::launch_digest(arena, ids, n, ~0ull, out, nullptr,
+                               static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
 // ---- coherence -------------------------------------------------------------------------
 int gdsm_coh_init(gdsm_ctx* ctx, uint32_t n_nodes) {
   if (!ctx || n_nodes == 0 || n_nodes > GDSM_MAX_NODES) return -EINVAL;

@@ -314,6 +314,10 @@ struct gdsm_comm {
   uint64_t fetch_serve_bytes = 0;
   uint8_t* fetch_recv = nullptr;   // requester: the pages asked of other ranks
   uint64_t fetch_recv_bytes = 0;
+  // conditional fetch (gdsm_fetch_changed): [G] changed pages per requester, [G] changed pages
+  // coming from each home, [G+1] the requesters' slices of this home's requests; pinned mirror
+  uint64_t* ccnt_dev = nullptr;
+  uint64_t* ccnt_host = nullptr;
 };
 
 using namespace gdsm::detail;
@@ -328,6 +332,8 @@ int comm_alloc(gdsm_comm* c) {
       hipHostMalloc(reinterpret_cast<void**>(&c->rcnt_host), words * 8) != hipSuccess ||
       hipMalloc(reinterpret_cast<void**>(&c->fcnt_dev), words * 8) != hipSuccess ||
       hipHostMalloc(reinterpret_cast<void**>(&c->fcnt_host), words * 8) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&c->ccnt_dev), words * 8) != hipSuccess ||
+      hipHostMalloc(reinterpret_cast<void**>(&c->ccnt_host), words * 8) != hipSuccess ||
       hipMalloc(reinterpret_cast<void**>(&c->verdict), 4 * (size_t)c->nranks) != hipSuccess)
     return -ENOMEM;
   return 0;
@@ -442,6 +448,8 @@ int gdsm_comm_fini(gdsm_comm* c) {
   if (c->rcnt_host) (void)hipHostFree(c->rcnt_host);
   if (c->fcnt_dev) (void)hipFree(c->fcnt_dev);
   if (c->fcnt_host) (void)hipHostFree(c->fcnt_host);
+  if (c->ccnt_dev) (void)hipFree(c->ccnt_dev);
+  if (c->ccnt_host) (void)hipHostFree(c->ccnt_host);
   for (uint8_t* p : {c->route_buf, c->pre, c->blk, c->blk_off, c->staging, c->fetch_serve,
                      c->fetch_recv})
     if (p) (void)hipFree(p);
@@ -888,6 +896,158 @@ int gdsm_fetch(gdsm_ctx* ctx, gdsm_comm* c, const uint32_t* pages, const uint32_
   if (late) return late;
   GDSM_TRY(gdsm::launch_fetch_scatter(c->fetch_recv, pages, dst_ids, h[2 * G + me], h[me], remote,
                                       ctx->n_pages, a0, a1, ctx->err, s));
+  return 0;
+}
+
+// ---- conditional fetch (SPEC §11) ----------------------------------------------------------
+// gdsm_fetch's split, counts and one agreement; then digests out, flags and only the changed pages
+// back. The sizes of the second group are known only after the homes have compared, so the changed
+// counts go all-to-all and are read on the host: the second synchronisation of the call.
+int gdsm_fetch_changed(gdsm_ctx* ctx, gdsm_comm* c, const uint32_t* pages, const uint32_t* dst_ids,
+                       uint64_t n, uint64_t total_pages, int src, uint32_t dst_arenas,
+                       uint32_t* changed, uint64_t* stats) {
+  if (!ctx || !c || (n && !pages)) return -EINVAL;
+  constexpr uint32_t kCur = 1u << GDSM_CURRENT, kTwin = 1u << GDSM_TWIN;
+  if (dst_arenas == 0) dst_arenas = kCur | kTwin;
+  if (src < 0 || src > 2 || (dst_arenas & ~(kCur | kTwin)) || ((dst_arenas >> src) & 1u))
+    return -EINVAL;
+  if (!ctx->arena[src] || ((dst_arenas & kCur) && !ctx->arena[GDSM_CURRENT]) ||
+      ((dst_arenas & kTwin) && !ctx->arena[GDSM_TWIN]))
+    return -EINVAL;
+  if (c->device != ctx->device || c->nranks > (int)gdsm::kFetchMaxRanks || total_pages == 0 ||
+      total_pages > GDSM_MAX_COH_PAGES)
+    return -EINVAL;
+  if (recording(ctx)) return -EBUSY;  // the call reads counts back on the host, twice
+  const int G = c->nranks, me = c->rank;
+  Transport* xp = c->xp;
+  CtxGuard g(ctx);
+  if (g.rc) return g.rc;
+  hipStream_t s = ctx->stream;
+  const uint64_t per = (total_pages + G - 1) / G;
+  const uint64_t base = (uint64_t)me * per < total_pages ? (uint64_t)me * per : total_pages;
+  const uint64_t end = ((uint64_t)me + 1) * per < total_pages ? ((uint64_t)me + 1) * per : total_pages;
+  const uint64_t block = end - base;
+  uint64_t* cnt = c->fcnt_dev;  // [0,G) requested, [G,2G) received, [2G,3G+1) bounds, [4G] flag
+  uint32_t* flag = reinterpret_cast<uint32_t*>(cnt + 4 * G);
+  int local = 0;
+  {
+    hipError_t e = hipMemsetAsync(flag, 0, 8, s);
+    if (e == hipSuccess)
+      e = gdsm::launch_fetch_split(pages, dst_ids, n, total_pages, per, (uint32_t)G, ctx->n_pages,
+                                   cnt, cnt + 2 * G, flag, s);
+    if (e != hipSuccess) {  // ask for nothing; the agreement below refuses everywhere
+      local = map_err(e);
+      (void)hipMemsetAsync(cnt, 0, 8 * (4 * (size_t)G + 1), s);
+    }
+  }
+  int rc = xp->all_to_all_u64(cnt, cnt + G, 1, s);
+  if (rc) return rc;
+  uint64_t* h = c->fcnt_host;
+  GDSM_TRY(hipMemcpyAsync(h, cnt, 8 * (4 * (size_t)G + 1), hipMemcpyDeviceToHost, s));
+  GDSM_TRY(hipStreamSynchronize(s));
+  std::vector<uint64_t> off(G + 1, 0), roff(G + 1, 0);  // as gdsm_fetch
+  for (int p = 0; p < G; ++p) {
+    off[p + 1] = off[p] + (p == me ? 0 : h[G + p]);
+    roff[p + 1] = roff[p] + (p == me ? 0 : h[p]);
+  }
+  const uint64_t served = off[G], remote = roff[G];
+  const uint64_t kPg = GDSM_PAGE_SZ;
+  const uint64_t nbs = gdsm::fetchc_pos_blocks(served), nbr = gdsm::fetchc_pos_blocks(remote);
+  // worst case, every page changed. Home: per request the page, its offered digest (16 B), id,
+  // flag and position (4 B each); requester: per remote entry the page, its digest, flag and
+  // position; both the positions' total and the scan's block words
+  if (!local)
+    local = ensure(ctx, &c->fetch_serve, &c->fetch_serve_bytes, served * (kPg + 28) + 8 * nbs + 4);
+  if (!local)
+    local = ensure(ctx, &c->fetch_recv, &c->fetch_recv_bytes, remote * (kPg + 24) + 8 * nbr + 4);
+  const bool invalid = (reinterpret_cast<uint32_t*>(h + 4 * G)[0] & 1u) || block > ctx->n_pages;
+  uint64_t verdict = (local ? kVerdictLocal : 0u) | (invalid ? 2u : 0u);
+  rc = xp->agree_max(&verdict, s);
+  if (rc) return rc;
+  if (verdict & kVerdictLocal) return refused(local);
+  if (verdict & 2) return -EINVAL;
+
+  const bool both = dst_arenas == (kCur | kTwin);
+  uint8_t* a0 = ctx->arena[(dst_arenas & kCur) ? GDSM_CURRENT : GDSM_TWIN];
+  uint8_t* a1 = both ? ctx->arena[GDSM_TWIN] : nullptr;
+  uint64_t* sdig = reinterpret_cast<uint64_t*>(c->fetch_serve + served * kPg);
+  uint32_t* req = reinterpret_cast<uint32_t*>(sdig + 2 * served);
+  uint32_t *sflags = req + served, *spos = sflags + served, *sblk = spos + served + 1;
+  uint64_t* rdig = reinterpret_cast<uint64_t*>(c->fetch_recv + remote * kPg);
+  uint32_t* rflags = reinterpret_cast<uint32_t*>(rdig + 2 * remote);
+  uint32_t *rpos = rflags + remote, *rblk = rpos + remote + 1;
+  uint64_t* cc = c->ccnt_dev;  // [0,G) changed per requester, [G,2G) from each home, [2G,3G+1) off
+  uint64_t* ch = c->ccnt_host;
+  int late = 0;  // a launch error of this rank once the peers are committed to the transfers
+  auto keep = [&late](hipError_t e) {
+    if (e != hipSuccess && !late) late = map_err(e);
+  };
+  gdsm::ProfScope ps(ctx->P(), GDSM_PROF_FETCH, s);
+  if (stats) keep(hipMemsetAsync(stats, 0, 32, s));
+  // pages homed here: compared and copied arena to arena
+  keep(gdsm::launch_fetchc_local(ctx->arena[src], pages, dst_ids, h[2 * G + me], h[me], base, block,
+                                 ctx->n_pages, a0, a1, changed, stats, ctx->err, s));
+  // the digests of this rank's copies of the pages homed elsewhere
+  keep(gdsm::launch_fetchc_offer(a0, pages, dst_ids, h[2 * G + me], h[me], remote, ctx->n_pages,
+                                 rdig, ctx->err, s));
+  // ids and digests to the homes
+  rc = xp->group_start();
+  for (int p = 0; p < G && !rc; ++p) {
+    if (p == me) continue;
+    if (h[p]) {
+      rc = xp->send(pages + h[2 * G + p], 4 * h[p], p, s);
+      if (!rc) rc = xp->send(rdig + 2 * roff[p], 16 * h[p], p, s);
+    }
+    if (!rc && h[G + p]) {
+      rc = xp->recv(req + off[p], 4 * h[G + p], p, s);
+      if (!rc) rc = xp->recv(sdig + 2 * off[p], 16 * h[G + p], p, s);
+    }
+  }
+  int rc2 = xp->group_end(s);
+  if (rc || rc2) return rc ? rc : rc2;
+  // the home compares, numbers the changed pages and counts them per requester
+  keep(gdsm::launch_fetchc_verify(ctx->arena[src], req, sdig, served, base, block, sflags,
+                                  ctx->err, s));
+  keep(gdsm::launch_fetchc_pos(sflags, served, sblk, sblk + nbs, spos, s));
+  for (int p = 0; p <= G; ++p) ch[2 * G + p] = off[p];
+  keep(hipMemcpyAsync(cc + 2 * G, ch + 2 * G, 8 * ((size_t)G + 1), hipMemcpyHostToDevice, s));
+  keep(gdsm::launch_fetchc_slices(spos, cc + 2 * G, (uint32_t)G, cc, s));
+  if (late) {  // this home's flags cannot be trusted: it sends "nothing changed" and no page
+    (void)hipMemsetAsync(sflags, 0, 4 * (served ? served : 1), s);
+    (void)hipMemsetAsync(cc, 0, 8 * (size_t)G, s);
+  }
+  rc = xp->all_to_all_u64(cc, cc + G, 1, s);
+  if (rc) return rc;
+  GDSM_TRY(hipMemcpyAsync(ch, cc, 16 * (size_t)G, hipMemcpyDeviceToHost, s));
+  GDSM_TRY(hipStreamSynchronize(s));
+  // cpre: where each requester's changed pages start in this home's staging; rpre: where each
+  // home's pages land in the requester's. Both sides bound a count by the requests it answers.
+  std::vector<uint64_t> cpre(G + 1, 0), rpre(G + 1, 0);
+  for (int p = 0; p < G; ++p) {
+    const uint64_t out = p == me ? 0 : (ch[p] < h[G + p] ? ch[p] : h[G + p]);
+    const uint64_t in = p == me ? 0 : (ch[G + p] < h[p] ? ch[G + p] : h[p]);
+    cpre[p + 1] = cpre[p] + out;
+    rpre[p + 1] = rpre[p] + in;
+  }
+  keep(gdsm::launch_fetchc_gather(ctx->arena[src], req, sflags, spos, served, base, block,
+                                  c->fetch_serve, s));
+  // flags and the changed pages back to the requesters
+  rc = xp->group_start();
+  for (int p = 0; p < G && !rc; ++p) {
+    if (p == me) continue;
+    const uint64_t out = cpre[p + 1] - cpre[p], in = rpre[p + 1] - rpre[p];
+    if (h[G + p]) rc = xp->send(sflags + off[p], 4 * h[G + p], p, s);
+    if (!rc && out) rc = xp->send(c->fetch_serve + cpre[p] * kPg, kPg * out, p, s);
+    if (!rc && h[p]) rc = xp->recv(rflags + roff[p], 4 * h[p], p, s);
+    if (!rc && in) rc = xp->recv(c->fetch_recv + rpre[p] * kPg, kPg * in, p, s);
+  }
+  rc2 = xp->group_end(s);
+  if (rc || rc2) return rc ? rc : rc2;
+  if (late) return late;
+  GDSM_TRY(gdsm::launch_fetchc_pos(rflags, remote, rblk, rblk + nbr, rpos, s));
+  GDSM_TRY(gdsm::launch_fetchc_place(c->fetch_recv, pages, dst_ids, rflags, rpos, h[2 * G + me],
+                                     h[me], remote, ctx->n_pages, a0, a1, changed, stats, ctx->err,
+                                     s));
   return 0;
 }
 

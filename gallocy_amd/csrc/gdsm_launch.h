@@ -223,6 +223,49 @@ hipError_t launch_fetch_list(const uint64_t* notices, uint64_t n, uint32_t want,
                              uint64_t* blk_off, uint64_t* total, uint32_t* out, uint64_t cap,
                              hipStream_t s);
 
+// Page digest (SPEC §10; gdsm_digest.hip): out[2i], out[2i+1] = (S0, S1) of page ids[i] (NULL:
+// page i) of arena; an id >= n_pages gets (0, 0) and err |= 8 (err may be NULL when n_pages is ~0:
+// raw callers). No workspace, one launch.
+hipError_t launch_digest(const uint8_t* arena, const uint32_t* ids, uint64_t n, uint64_t n_pages,
+                         uint64_t* out, uint32_t* err, hipStream_t s, Prof* prof = nullptr);
+
+// Conditional fetch (SPEC §11; gdsm_digest.hip). List arguments as the fetch launchers above.
+// Requester: dig[2k], dig[2k+1] = the digest of a's page dst(i) for its k-th entry homed elsewhere.
+hipError_t launch_fetchc_offer(const uint8_t* a, const uint32_t* pages, const uint32_t* dst_ids,
+                               uint64_t skip_at, uint64_t skip, uint64_t cnt, uint64_t n_pages,
+                               uint64_t* dig, uint32_t* err, hipStream_t s);
+// Home: flags[j] = 1 when src's page req[j] - base does not have the digest dig[2j], dig[2j+1];
+// 0 for a request outside [base, base + block) (err |= 8).
+hipError_t launch_fetchc_verify(const uint8_t* src, const uint32_t* req, const uint64_t* dig,
+                                uint64_t n, uint64_t base, uint64_t block, uint32_t* flags,
+                                uint32_t* err, hipStream_t s);
+// pos[i] = the set flags before entry i, pos[m] = their total (m + 1 words); blk and blk_off hold
+// fetchc_pos_blocks(m) u32 each.
+uint64_t fetchc_pos_blocks(uint64_t m);
+hipError_t launch_fetchc_pos(const uint32_t* flags, uint64_t m, uint32_t* blk, uint32_t* blk_off,
+                             uint32_t* pos, hipStream_t s);
+// counts[p] = pos[off[p+1]] - pos[off[p]] for the G slices off[G+1] (device) of the home's requests.
+hipError_t launch_fetchc_slices(const uint32_t* pos, const uint64_t* off, uint32_t G,
+                                uint64_t* counts, hipStream_t s);
+// Home: staging[pos[j]] := page req[j] - base of src for the requests with flags[j] set.
+hipError_t launch_fetchc_gather(const uint8_t* src, const uint32_t* req, const uint32_t* flags,
+                                const uint32_t* pos, uint64_t n, uint64_t base, uint64_t block,
+                                uint8_t* staging, hipStream_t s);
+// Requester: its cnt entries homed elsewhere; with flags[k] set, staging page pos[k] into a0 / a1,
+// otherwise a1 (when not NULL) := a0's page. changed (n entries) and stats (4 u64: [0] += the
+// entries replaced, [1] += the entries kept) may be NULL.
+hipError_t launch_fetchc_place(const uint8_t* staging, const uint32_t* pages,
+                               const uint32_t* dst_ids, const uint32_t* flags, const uint32_t* pos,
+                               uint64_t skip_at, uint64_t skip, uint64_t cnt, uint64_t n_pages,
+                               uint8_t* a0, uint8_t* a1, uint32_t* changed, uint64_t* stats,
+                               uint32_t* err, hipStream_t s);
+// Requester and home at once: entries [first, first + cnt) compared byte for byte with src's page
+// pages[i] - base; a0 is stored when it differs, a1 (when not NULL) always. stats[2] / [3].
+hipError_t launch_fetchc_local(const uint8_t* src, const uint32_t* pages, const uint32_t* dst_ids,
+                               uint64_t first, uint64_t cnt, uint64_t base, uint64_t block,
+                               uint64_t n_pages, uint8_t* a0, uint8_t* a1, uint32_t* changed,
+                               uint64_t* stats, uint32_t* err, hipStream_t s);
+
 // GPU NW alignment (legacy diff()): workspace per pair and the fill + trace launches.
 uint64_t nw_pair_ws_bytes(uint32_t max_len);
 hipError_t launch_nw(const uint8_t* a, const uint64_t* a_off, const uint8_t* b,

@@ -471,3 +471,20 @@ def fetch(ctx: gdsm.Context, comm: Comm, pages, dst_ids, n: int, total_pages: in
     check(gdsm.lib().gdsm_fetch(ctx.handle, comm.handle, gdsm.Context._ptr(pages),
                                 gdsm.Context._ptr(dst_ids), n, total_pages, gdsm._ARENA[src],
                                 mask), "gdsm_fetch")
+
+
+def fetch_changed(ctx: gdsm.Context, comm: Comm, pages, dst_ids, n: int, total_pages: int,
+                  src=gdsm.REPLICA, dst=("current", "twin"), changed=None, stats=None):
+    """gdsm_fetch_changed (SPEC §11; collective): gdsm_fetch's result, moving only the pages whose
+    copy at this rank (arena CURRENT when named, else TWIN, at the destination) differs from the home
+    copy: remote entries are compared by their 16-byte digests (§10), entries homed here byte for
+    byte. changed (device, n u32) and stats (device, 4 u64: remote transferred, remote skipped,
+    local differing, local equal) are optional outputs. Enqueued on ctx's stream; sync before
+    reading the arenas or the outputs."""
+    mask = 0
+    for a in dst:
+        mask |= 1 << gdsm._ARENA[a]
+    check(gdsm.lib().gdsm_fetch_changed(ctx.handle, comm.handle, gdsm.Context._ptr(pages),
+                                        gdsm.Context._ptr(dst_ids), n, total_pages,
+                                        gdsm._ARENA[src], mask, gdsm.Context._ptr(changed),
+                                        gdsm.Context._ptr(stats)), "gdsm_fetch_changed")

@@ -252,7 +252,7 @@ class Context:
         return Graph(g.value)
 
     PROF_STAGES = ("diff", "apply", "twin", "coh_fold", "coh_reduce", "nw_fill", "nw_trace",
-                   "exchange", "route", "exchange_wait", "merge", "fetch")
+                   "exchange", "route", "exchange_wait", "merge", "fetch", "digest")
 
     def prof_enable(self, on: bool = True):
         check(lib().gdsm_prof_enable(self.handle, int(on)), "gdsm_prof_enable")
@@ -398,6 +398,18 @@ class Context:
         check(lib().gdsm_merge(self.handle, K, arr, idp, self._ptr(d_out), n_out, C.byref(out.s),
                                self._ptr(conflicts), stats.ptr), "gdsm_merge")
         return MergeResult(self, out, d_out, stats, conflicts, n_out, own)
+
+    def digest(self, arena="current", ids=None, n: Optional[int] = None,
+               out: Optional[DeviceBuffer] = None) -> DeviceBuffer:
+        """gdsm_digest (docs/SPEC.md §10): the 16-byte digests (S0, S1) of pages `ids` (a
+        DeviceBuffer or device pointer; None = pages 0..n-1) of `arena` into `out` (2n uint64 on the
+        device; allocated here when None). Asynchronous, recordable; read the result with
+        out.download(np.uint64, 2 * n).reshape(n, 2) after a sync."""
+        n = self._count(ids, n)
+        out = out or self.buffer(16 * max(n, 1))
+        check(lib().gdsm_digest(self.handle, _ARENA[arena], self._ptr(ids), n, out.ptr),
+              "gdsm_digest")
+        return out
 
     def _count(self, ids, n):
         if n is not None:

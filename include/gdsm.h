@@ -72,6 +72,7 @@ enum gdsm_prof_stage {
   GDSM_PROF_EXCHANGE_WAIT, /* gdsm_exchange: the transfer plus the wait for the peers' streams */
   GDSM_PROF_MERGE,      /* gdsm_merge: its check, size, scan and emit launches together */
   GDSM_PROF_FETCH,      /* gdsm_fetch: its two transfer groups and the gather / scatter launches */
+  GDSM_PROF_DIGEST,     /* gdsm_digest: digest_kernel */
   GDSM_PROF_STAGES
 };
 
@@ -571,6 +572,55 @@ int gdsm_fetch(gdsm_ctx* ctx, gdsm_comm* comm, const uint32_t* pages, const uint
  * n > GDSM_MAX_COH_PAGES; -EBUSY on a recording context. */
 int gdsm_notices_fetch_list(gdsm_ctx* ctx, const uint64_t* notices, uint64_t n, uint32_t want,
                             uint32_t* pages_out, uint64_t cap, uint64_t* n_out);
+
+/* ---- page digest (docs/SPEC.md §10) -----------------------------------------------------------
+ * A page's identity in 16 bytes: two u64 (S0, S1) over its 1024 little-endian u32 words x[],
+ *   S_t = sum_{i < 512} ((x[2i] + K[2i + 4t]) mod 2^32) * ((x[2i+1] + K[2i+1 + 4t]) mod 2^32) mod 2^64,
+ * t = 0, 1, with the public keys K[j] = mix64(j + 1) >> 32 (SPEC §6's mix64): the NH construction of
+ * UMAC with two Toeplitz-shifted key rows. It is a sum, so the bits do not depend on the reduction
+ * order. Like the wire checksum (§7) it is NOT a MAC: two unrelated pages collide with probability
+ * about 2^-64, a colliding pair can be constructed. Use it to learn that two copies are equal
+ * without moving them (gdsm_fetch_changed below; a Raft follower's REPLICA against its leader's).
+ *
+ * out (device, 2n u64): (S0, S1) of page ids[i] (NULL: page i) of arena `which`. Asynchronous on the
+ * context stream, no host synchronisation, no workspace (may be recorded into a graph). ids may
+ * repeat. An id >= gdsm_n_pages(ctx) gets (0, 0) and the next gdsm_sync reports -EINVAL.
+ * Immediate -EINVAL: NULL ctx, a bad `which`, an arena the context lacks, n without out. n == 0 is
+ * a no-op. With profiling on, GDSM_PROF_DIGEST times the launch. */
+int gdsm_digest(gdsm_ctx* ctx, int which, const uint32_t* ids, uint64_t n, uint64_t* out);
+/* The same on a caller's arena and stream, ids unchecked (NULL: pages 0 .. n-1). */
+int gdsm_digest_raw(const uint8_t* arena, const uint32_t* ids, uint64_t n, uint64_t* out,
+                    void* stream);
+
+/* ---- conditional fetch: move only the stale pages (docs/SPEC.md §11) --------------------------
+ * gdsm_fetch with the question "do you already have it?" asked first. Arguments, list rules, home
+ * mapping, ordering (after pending gdsm_exchange / gdsm_apply_async work, no gdsm_sync needed),
+ * -EBUSY on a recording context and every immediate and collective refusal are gdsm_fetch's.
+ * Postcondition on the arenas: gdsm_fetch's, provided no digest collides: every named arena at
+ * dst(i) equals the home copy of pages[i], nothing else changes anywhere, src is only read.
+ *
+ * What travels differs. The requester's existing copy is arena A at dst(i), A = CURRENT when it is
+ * named, else TWIN.
+ *   entries homed at another rank: the requester sends the 4-B id and the 16-B digest of A[dst(i)];
+ *     the home digests its own page and answers one u32 flag per entry plus the 4 KiB pages of the
+ *     entries whose digests differ, compacted in request order. A matching entry moves no page;
+ *     with both arenas named the other arena is made equal by a device-local copy of A[dst(i)], so
+ *     the page still arrives clean.
+ *   entries homed at the caller: compared byte for byte with the home copy on the device (exact, no
+ *     digest), copied arena to arena when they differ.
+ *   changed    device, n u32, may be NULL: changed[i] = 1 when entry i's contents in A were
+ *              replaced, 0 when they were found equal (exactly for local entries, by digest for
+ *              remote ones);
+ *   stats      device, 4 u64, may be NULL, over this rank's list: [0] remote entries transferred,
+ *              [1] remote entries skipped, [2] local entries that differed, [3] local entries found
+ *              equal. Written (zeroed, then counted) only when the call is not refused.
+ * Sending only what changed costs a second host synchronisation: the homes' changed counts go
+ * all-to-all and are read back before the pages move (gdsm_fetch reads the host once).
+ * Memory: the staging buffers of gdsm_fetch, sized for the worst case (every page changed) plus
+ * about 32 B per served request at a home and per remote entry at a requester. */
+int gdsm_fetch_changed(gdsm_ctx* ctx, gdsm_comm* comm, const uint32_t* pages,
+                       const uint32_t* dst_ids, uint64_t n, uint64_t total_pages, int src,
+                       uint32_t dst_arenas, uint32_t* changed, uint64_t* stats);
 
 const char* gdsm_version(void);
 /* Process-wide kernel-variant knobs for measurement (every value produces the same results):
