@@ -129,6 +129,10 @@ SIGNATURES = {
     "gdsm_digest_raw": (C.c_int, [vp, vp, C.c_uint64, vp, vp]),
     "gdsm_fetch_changed": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32,
                                      vp, vp]),
+    "gdsm_dirty_scan": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_uint64, vp, vp, C.c_uint64, vp]),
+    "gdsm_dirty_scan_workspace_bytes": (C.c_uint64, [C.c_uint64]),
+    "gdsm_dirty_scan_raw": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp,
+                                      C.c_uint64, vp]),
     "gdsm_exchange": (C.c_int, [vp, vp, C.POINTER(GdsmRuns), C.POINTER(vp), C.POINTER(GdsmRuns),
                                 C.POINTER(vp), C.c_int, C.c_uint32]),
 }

@@ -271,6 +271,7 @@ int gdsm_fini(gdsm_ctx* ctx) {
   if (ctx->wire_ws) (void)hipFree(ctx->wire_ws);
   if (ctx->merge_ws) (void)hipFree(ctx->merge_ws);
   if (ctx->fetch_ws) (void)hipFree(ctx->fetch_ws);
+  if (ctx->dirty_ws) (void)hipFree(ctx->dirty_ws);
   for (auto* p : ctx->ids_safe)
     if (p) (void)hipFree(p);
   for (auto& kv : ctx->runs_busy) (void)hipEventDestroy(kv.second);
@@ -901,6 +902,43 @@ int gdsm_digest_raw(const uint8_t* arena, const uint32_t* ids, uint64_t n, uint6
   if (!arena || (n && !out)) return -EINVAL;
   GDSM_TRY(gdsm::launch_digest(arena, ids, n, ~0ull, out, nullptr,
                                static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+// ---- dirty scan (SPEC §12) ---------------------------------------------------------------
+uint64_t gdsm_dirty_scan_workspace_bytes(uint64_t n) { return gdsm::dirty_workspace_bytes(n); }
+
+// The refusals both forms share: a list longer than 2^32, a capacity with nowhere to write.
+static bool dirty_args_bad(uint64_t n, const uint32_t* pages_out, const uint32_t* pos_out,
+                           uint64_t cap) {
+  return n > (1ull << 32) || (cap > 0 && !pages_out && !pos_out);
+}
+
+int gdsm_dirty_scan(gdsm_ctx* ctx, int a, int b, const uint32_t* ids, uint64_t n,
+                    uint32_t* pages_out, uint32_t* pos_out, uint64_t cap, uint64_t* stats) {
+  if (!ctx || a < 0 || a > 2 || b < 0 || b > 2 || a == b || !ctx->arena[a] || !ctx->arena[b])
+    return -EINVAL;
+  if (dirty_args_bad(n, pages_out, pos_out, cap)) return -EINVAL;
+  CtxGuard g(ctx);
+  if (g.rc) return g.rc;
+  int rc = n ? ensure(ctx, &ctx->dirty_ws, &ctx->dirty_ws_bytes, gdsm::dirty_workspace_bytes(n)) : 0;
+  if (rc) return rc;
+  GDSM_TRY(gdsm::launch_dirty_scan(ctx->arena[a], ctx->arena[b], ids, n, ctx->n_pages, pages_out,
+                                   pos_out, cap, stats, ctx->err, ctx->dirty_ws,
+                                   ctx->dirty_ws_bytes, ctx->stream));
+  return 0;
+}
+
+int gdsm_dirty_scan_raw(const uint8_t* a, const uint8_t* b, const uint32_t* ids, uint64_t n,
+                        uint32_t* pages_out, uint32_t* pos_out, uint64_t cap, uint64_t* stats,
+                        void* workspace, uint64_t workspace_bytes, void* stream) {
+  if (!a || !b || dirty_args_bad(n, pages_out, pos_out, cap)) return -EINVAL;
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 7) ||
+      workspace_bytes < gdsm::dirty_workspace_bytes(n))
+    return -EINVAL;
+  GDSM_TRY(gdsm::launch_dirty_scan(a, b, ids, n, ~0ull, pages_out, pos_out, cap, stats, nullptr,
+                                   static_cast<uint8_t*>(workspace), workspace_bytes,
+                                   static_cast<hipStream_t>(stream)));
   return 0;
 }
 

@@ -65,6 +65,9 @@ struct gdsm_ctx {
   // gdsm_notices_fetch_list: block counts, their offsets and the total
   uint8_t* fetch_ws = nullptr;
   uint64_t fetch_ws_bytes = 0;
+  // gdsm_dirty_scan: tile offsets, flag words and bounds
+  uint8_t* dirty_ws = nullptr;
+  uint64_t dirty_ws_bytes = 0;
   // checked copies of caller page-id lists (launch_check_ids): one per stream, so an async
   // apply's list is never overwritten by a call on the main stream
   // [2]: the target-page list of gdsm_diff_apply_ids (main stream, beside [0])

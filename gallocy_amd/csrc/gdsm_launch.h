@@ -266,6 +266,19 @@ hipError_t launch_fetchc_local(const uint8_t* src, const uint32_t* pages, const 
                                uint64_t n_pages, uint8_t* a0, uint8_t* a1, uint32_t* changed,
                                uint64_t* stats, uint32_t* err, hipStream_t s);
 
+// Dirty scan (SPEC §12; gdsm_dirty.hip): the entries i of the list ids[0..n) (NULL: the identity)
+// whose page differs between arenas a and b, compacted in list order: pages_out[k] = the page,
+// pos_out[k] = i (either may be NULL), the first cap of them; stats (2 x u64, may be NULL) = their
+// number and the sum of min(10244, 4 + 48 x differing 16-B chunks) over them. An id >= n_pages is
+// not dirty and err |= 8 (err may be NULL when n_pages is ~0: raw callers). ws: 8-byte aligned,
+// dirty_workspace_bytes(n), its contents need not be kept. Three launches on s (n == 0: one
+// memset), no host synchronisation.
+uint64_t dirty_workspace_bytes(uint64_t n);
+hipError_t launch_dirty_scan(const uint8_t* a, const uint8_t* b, const uint32_t* ids, uint64_t n,
+                             uint64_t n_pages, uint32_t* pages_out, uint32_t* pos_out,
+                             uint64_t cap, uint64_t* stats, uint32_t* err, uint8_t* ws,
+                             uint64_t ws_bytes, hipStream_t s);
+
 // GPU NW alignment (legacy diff()): workspace per pair and the fill + trace launches.
 uint64_t nw_pair_ws_bytes(uint32_t max_len);
 hipError_t launch_nw(const uint8_t* a, const uint64_t* a_off, const uint8_t* b,

@@ -177,6 +177,36 @@ class MergeResult:
                 b.free()
 
 
+class DirtyList:
+    """What Context.dirty_scan returns: `pages` (DeviceBuffer of the dirty entries' pages, None for
+    the count-only form), `pos` (DeviceBuffer of their list positions, None without want_pos),
+    `cap` (the entries both hold), and `count` / `bound` (lazy reads that synchronise; a graph
+    replay of the scan refreshes them)."""
+
+    def __init__(self, ctx, pages, pos, stats, cap):
+        self.ctx, self.pages, self.pos, self.cap = ctx, pages, pos, cap
+        self._stats = stats
+
+    def _read(self) -> np.ndarray:
+        self.ctx.sync()
+        return self._stats.download(np.uint64, 2)
+
+    @property
+    def count(self) -> int:
+        """The number of dirty entries, also when it exceeds cap (synchronises)."""
+        return int(self._read()[0])
+
+    @property
+    def bound(self) -> int:
+        """Upper bound of the diff stream of the dirty entries, in bytes (synchronises)."""
+        return int(self._read()[1])
+
+    def free(self):
+        for b in (self.pages, self.pos, self._stats):
+            if b is not None and b.ptr:
+                b.free()
+
+
 class Graph:
     """An instantiated HIP graph of recorded libgdsm calls (Context.capture_end)."""
 
@@ -410,6 +440,22 @@ class Context:
         check(lib().gdsm_digest(self.handle, _ARENA[arena], self._ptr(ids), n, out.ptr),
               "gdsm_digest")
         return out
+
+    def dirty_scan(self, a="twin", b="current", ids=None, n: Optional[int] = None,
+                   cap: Optional[int] = None, want_pos: bool = False) -> "DirtyList":
+        """gdsm_dirty_scan (docs/SPEC.md §12): the entries of `ids` (a DeviceBuffer or device
+        pointer; None = pages 0..n-1) whose page differs between arenas `a` and `b`, compacted in
+        list order. cap: the entries the output holds (None: n; 0: count only). Asynchronous,
+        recordable once the workspace has its size; DirtyList.count / .bound synchronise."""
+        n = self._count(ids, n)
+        cap = n if cap is None else int(cap)
+        pages = self.buffer(4 * max(cap, 1)) if cap else None
+        pos = self.buffer(4 * max(cap, 1)) if cap and want_pos else None
+        stats = self.buffer(16)
+        check(lib().gdsm_dirty_scan(self.handle, _ARENA[a], _ARENA[b], self._ptr(ids), n,
+                                    self._ptr(pages), self._ptr(pos), cap, stats.ptr),
+              "gdsm_dirty_scan")
+        return DirtyList(self, pages, pos, stats, cap)
 
     def _count(self, ids, n):
         if n is not None:

@@ -622,6 +622,44 @@ int gdsm_fetch_changed(gdsm_ctx* ctx, gdsm_comm* comm, const uint32_t* pages,
                        const uint32_t* dst_ids, uint64_t n, uint64_t total_pages, int src,
                        uint32_t dst_arenas, uint32_t* changed, uint64_t* stats);
 
+/* ---- dirty scan: which pages did this interval change? (docs/SPEC.md §12) --------------------
+ * The device counterpart of gdsm_track_dirty, for a writer that takes no faults (a kernel storing
+ * into CURRENT): the list of pages that gdsm_diff / gdsm_release / gdsm_exchange / gdsm_merge take
+ * from their caller, made by comparing two arenas of the context.
+ *   a, b       two different arena kinds the context holds; the usual pair is GDSM_TWIN,
+ *              GDSM_CURRENT (GDSM_REPLICA, GDSM_CURRENT: "which pages differ from my home copy");
+ *   ids        device, n page ids, or NULL for pages 0 .. n-1; need not be sorted, may repeat, each
+ *              entry is judged on its own;
+ *   pages_out  device, cap u32, may be NULL: the pages of the dirty entries, in list order (a
+ *              stable compaction: strictly ascending when the list is, or with no list);
+ *   pos_out    device, cap u32, may be NULL: the list positions i of the same entries (to gather
+ *              gdsm_release's target_ids);
+ *   stats      device, 2 u64, may be NULL: [0] the number of dirty entries, also when it exceeds
+ *              cap (then only the first cap are written and nothing at or past [cap]); [1] an upper
+ *              bound of rec_off[count] of the diff (a -> b) of the dirty entries, the sum over them
+ *              of min(10244, 4 + 48 C), C = the 16-B chunks of the page in which a and b differ:
+ *              the capacity to give gdsm_runs_alloc in place of count x 10244.
+ * Entry i is dirty iff page ids[i] of a and of b differ in at least one byte. cap == 0 with both
+ * outputs NULL is the count-only form. An id >= gdsm_n_pages(ctx) is not dirty, contributes nothing
+ * and the next gdsm_sync reports -EINVAL. Both arenas are only read. n == 0 writes stats = {0, 0}
+ * and nothing else.
+ * Asynchronous on the context's stream, no host synchronisation: read stats after gdsm_sync. The
+ * workspace (at most 1 B per entry plus a constant) is the context's and only grows; a recording
+ * context that would have to grow it gets -EBUSY (scan once before recording, as gdsm_merge),
+ * otherwise the call can be recorded, and a replay reads the arenas again. Not timed by a
+ * gdsm_prof_stage.
+ * Immediate -EINVAL: NULL ctx, a == b, a bad kind, an arena the context lacks, n > 2^32, cap > 0
+ * with both outputs NULL. */
+int gdsm_dirty_scan(gdsm_ctx* ctx, int a, int b, const uint32_t* ids, uint64_t n,
+                    uint32_t* pages_out, uint32_t* pos_out, uint64_t cap, uint64_t* stats);
+/* The same on a caller's arenas, workspace (8-byte aligned, at least
+ * gdsm_dirty_scan_workspace_bytes(n) device bytes, contents need not be kept) and stream; ids are
+ * not checked. -EINVAL also for a NULL arena and a workspace that is NULL, misaligned or too small. */
+uint64_t gdsm_dirty_scan_workspace_bytes(uint64_t n);
+int gdsm_dirty_scan_raw(const uint8_t* a, const uint8_t* b, const uint32_t* ids, uint64_t n,
+                        uint32_t* pages_out, uint32_t* pos_out, uint64_t cap, uint64_t* stats,
+                        void* workspace, uint64_t workspace_bytes, void* stream);
+
 const char* gdsm_version(void);
 /* Process-wide kernel-variant knobs for measurement (every value produces the same results):
  * "diff_variant" 0..8 (diff geometry), "apply_variant" 0..7, "diff_solo_max" 0..16 and
