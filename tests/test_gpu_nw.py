@@ -1,7 +1,8 @@
 """GPU Needleman-Wunsch (gdsm_nw_diff_batch, the legacy diff() on the GPU) against the reference's
 own goldens, the vectors the reference produced (tests/golden/nw_ref.npz) and the C oracle
-(or_nw_diff <- gallocy/utils/diff.cpp:73-167) on seeded random pairs. Bit-exact: the outputs are
-bytes."""
+(or_nw_diff <- gallocy/utils/diff.cpp:73-167) on seeded random pairs, on the structured corpus of
+tests/nw_corpus.py (paths far from the trace's guessed strip entries) and around the launcher:
+chunked batches, stale workspace slots, output bounds. Bit-exact: the outputs are bytes."""
 import ctypes as C
 
 import numpy as np
@@ -126,6 +127,185 @@ def test_legacy_diff_symbol_offloaded(ctx):
         assert ga.diff(a, b) == want  # gdsm_nw_diff takes the same route
     finally:
         ga.set_diff_device(None)
+
+
+# ---- paths far from the trace's guessed strip entries, chunked launches, stale slots ----------
+def _check(pairs, got):
+    assert len(got) == len(pairs)
+    for i, ((a, b), g) in enumerate(zip(pairs, got)):
+        assert g == oracle.nw_diff(a, b), (i, len(a), len(b))
+
+
+def test_structured_corpus_vs_oracle(ctx):
+    """tests/nw_corpus.py: re-walks that merge on their first row, later or never, column-0
+    re-walks, row-0 runs, entries 600 columns off the guess (tests/test_nw_corpus.py pins that
+    the corpus reaches them). One batch, then pair by pair."""
+    from tests import nw_corpus
+    corpus = nw_corpus.corpus()
+    want = {name: oracle.nw_diff(a, b) for name, (a, b) in corpus.items()}
+    got = ctx.nw_diff_batch(list(corpus.values()))
+    for name, g in zip(corpus, got):
+        assert g == want[name], name
+    for name, pair in corpus.items():
+        assert ctx.nw_diff_batch([pair]) == [want[name]], name
+
+
+SWEEP_N1 = (511, 512, 513, 1023, 1024, 1025, 4095, 4096, 4097)
+SWEEP_N2 = (1, 2, 15, 16, 17, 49, 63, 64, 65, 127, 128, 129, 191, 192, 193, 194, 255, 256, 257, 300)
+# more than 8 strips and more than 80 columns: the last wave of a group hands its bottom row to
+# wave 0 through global memory while the 256-slot rings wrap, over several phases
+WIDE_GROUPS = ((4700, 900), (8200, 300), (4097, 257))
+
+
+@pytest.mark.parametrize("shapes,alphabet",
+                         [("sweep", 2), ("sweep", 4), ("wide", 4), ("wide", 256)])
+def test_boundary_sweep_vs_oracle(ctx, shapes, alphabet):
+    """Strip and group boundaries in n1 against lane, block, phase and ring boundaries in n2."""
+    rng = np.random.default_rng(1000 + alphabet + (shapes == "wide"))
+    dims = WIDE_GROUPS if shapes == "wide" else [(n1, n2) for n1 in SWEEP_N1 for n2 in SWEEP_N2]
+    pairs = [(_rand(rng, n1, alphabet), _rand(rng, n2, alphabet)) for n1, n2 in dims]
+    _check(pairs, ctx.nw_diff_batch(pairs))
+
+
+def test_zero_length_beside_long_pairs(ctx):
+    """The fill returns early for a pair with an empty string and leaves its workspace slot as
+    the previous launch wrote it; the trace of such a pair must read none of it."""
+    rng = np.random.default_rng(21)
+    dims = [(1500, 700), (1500, 0), (0, 1500), (600, 0), (0, 0), (513, 1), (1, 513), (1500, 700)]
+    pairs = [(_rand(rng, n1, 4), _rand(rng, n2, 4)) for n1, n2 in dims]
+    want = [oracle.nw_diff(a, b) for a, b in pairs]
+    assert ctx.nw_diff_batch(pairs) == want
+    assert ctx.nw_diff_batch(pairs) == want
+    # and once shifted by a slot: every empty pair in a slot a long pair has just filled
+    assert ctx.nw_diff_batch(pairs[-1:] + pairs[:-1]) == want[-1:] + want[:-1]
+
+
+def _pair_ws_bytes(max_len):
+    """Geo::per_pair() of gdsm_nw.hip restated: checkpoints, bottom rows and row records."""
+    strips = max(1, -(-max_len // 512))
+    blocks = (max_len + 63 + 15) // 16
+    ck = strips * ((blocks * 16 + 63) // 64) * 64 * 40
+    rows = (strips * (max_len + 64) * 4 + 255) & ~255
+    rec = ((max_len + 2) * 4 + 255) & ~255
+    return ck + rows + rec
+
+
+CHUNK_WS = 4 << 30  # gdsm_nw_diff_batch: at most this much workspace per launch
+
+
+@pytest.mark.parametrize("case", ["lds", "global_b"])
+def test_batch_cut_into_chunks(case):
+    """A max_len far above the strings sets the workspace strides and makes the launcher cut the
+    batch (first_pair > 0, slots reused from chunk to chunk)."""
+    rng = np.random.default_rng(31)
+    if case == "lds":
+        max_len, n = 49136, 45
+        dims = [tuple(int(v) for v in rng.integers(1, 1201, 2)) for _ in range(n)]
+        for i, d in {2: (0, 900), 7: (1100, 0), 19: (0, 0), 20: (1200, 1200), 23: (700, 0),
+                     39: (0, 1), 40: (513, 1199), 44: (1025, 64)}.items():
+            dims[i] = d
+        per_launch = [20, 20, 5]
+        for f in (0, 20, 40):  # every chunk has multi-strip pairs
+            assert sum(n1 > 512 for n1, _ in dims[f:f + 20]) >= 2
+    else:
+        max_len = 200000
+        dims = [(3000, 2900), (0, 40), (1537, 700), (1, 3000)]
+        per_launch = [1, 1, 1, 1]
+    chunk = CHUNK_WS // _pair_ws_bytes(max_len)
+    cuts = [min(chunk, len(dims) - f) for f in range(0, len(dims), max(chunk, 1))]
+    assert cuts == per_launch, (chunk, _pair_ws_bytes(max_len))
+    pairs = [(_rand(rng, n1, 4), _rand(rng, n2, 4)) for n1, n2 in dims]
+    with ga.Context(1, arenas=()) as c:
+        c.prof_enable()
+        got = c.nw_diff_batch(pairs, max_len=max_len)
+        prof = c.prof_read()
+        assert prof["nw_fill"][1] == len(per_launch) and prof["nw_trace"][1] == len(per_launch)
+        _check(pairs, got)
+        assert c.nw_diff_batch(pairs) == got
+        assert c.prof_read()["nw_fill"][1] == 1
+
+
+def test_b_staging_switch(ctx):
+    """max_len 49136 is the last at which the fill stages b in LDS; 49137 reads it from global
+    memory. The same pair, as long as the staging allows, through both."""
+    rng = np.random.default_rng(41)
+    a, b = _rand(rng, 60, 4), _rand(rng, 49136, 4)
+    want = [oracle.nw_diff(a, b)]
+    assert ctx.nw_diff_batch([(a, b)], max_len=49136) == want
+    assert ctx.nw_diff_batch([(a, b)], max_len=49137) == want
+
+
+def test_outputs_touch_only_their_bytes(ctx):
+    """Pair i owns |a_i| + |b_i| + 1 bytes at a_off[i] + b_off[i] + i of both outputs and writes
+    its L_i alignment bytes and one NUL there; nothing else in the buffers changes."""
+    rng = np.random.default_rng(51)
+    dims = [(700, 650), (0, 30), (30, 0), (1100, 40), (40, 1100), (0, 0), (513, 512), (64, 65),
+            (1, 1), (300, 299)]
+    pairs = [(_rand(rng, n1, 4), _rand(rng, n2, 4)) for n1, n2 in dims]
+    want = [oracle.nw_diff(a, b) for a, b in pairs]
+    n = len(pairs)
+    a_off = np.zeros(n + 1, np.uint64)
+    b_off = np.zeros(n + 1, np.uint64)
+    a_off[1:] = np.cumsum([n1 for n1, _ in dims])
+    b_off[1:] = np.cumsum([n2 for _, n2 in dims])
+    total = int(a_off[-1] + b_off[-1]) + n
+    tail = 256  # room behind the last slot, watched as well
+    ins = [np.frombuffer(b"".join(p[0] for p in pairs), np.uint8), a_off,
+           np.frombuffer(b"".join(p[1] for p in pairs), np.uint8), b_off]
+    bufs = [ctx.buffer(x.nbytes).upload(x) for x in ins]
+    o1 = ctx.buffer(total + tail).upload(np.full(total + tail, 0xA5, np.uint8))
+    o2 = ctx.buffer(total + tail).upload(np.full(total + tail, 0xA5, np.uint8))
+    ol = ctx.buffer(8 * (n + 1)).upload(np.full(n + 1, 2**64 - 1, np.uint64))
+    try:
+        _lib.check(_lib.load().gdsm_nw_diff_batch(ctx.handle, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr,
+                                                  bufs[3].ptr, n, 1100, o1.ptr, o2.ptr, ol.ptr))
+        h1, h2 = o1.download(np.uint8, total + tail), o2.download(np.uint8, total + tail)
+        lens = ol.download(np.uint64, n + 1)
+    finally:
+        for x in (*bufs, o1, o2, ol):
+            x.free()
+    assert sum(len(w[0]) < n1 + n2 for w, (n1, n2) in zip(want, dims)) >= 6  # slots with slack
+    assert lens.tolist() == [len(w[0]) for w in want] + [2**64 - 1]
+    e1, e2 = (np.full(total + tail, 0xA5, np.uint8) for _ in range(2))
+    for i, (w1, w2) in enumerate(want):
+        o = int(a_off[i] + b_off[i]) + i
+        assert len(w1) + 1 <= dims[i][0] + dims[i][1] + 1
+        e1[o:o + len(w1) + 1] = np.frombuffer(w1 + b"\0", np.uint8)
+        e2[o:o + len(w2) + 1] = np.frombuffer(w2 + b"\0", np.uint8)
+    assert np.array_equal(h1, e1) and np.array_equal(h2, e2)
+
+
+def test_diff_device_threshold(ctx):
+    """gdsm_set_diff_device(ctx, min_cells): n1 * n2 below min_cells stays on the CPU."""
+    rng = np.random.default_rng(61)
+    below = (_rand(rng, 199, 4), _rand(rng, 200, 4))
+    at = (_rand(rng, 200, 4), _rand(rng, 200, 4))
+    ctx.prof_enable()
+    ga.set_diff_device(ctx, 40000)
+    try:
+        assert ga.diff(*below) == oracle.nw_diff(*below)
+        assert ctx.prof_read()["nw_fill"][1] == 0
+        assert ga.diff(*at) == oracle.nw_diff(*at)
+        assert ctx.prof_read()["nw_fill"][1] == 1
+    finally:
+        ga.set_diff_device(None)
+        ctx.prof_enable(False)
+
+
+def test_batch_argument_checks(ctx):
+    """Refused or finished before any launch."""
+    fn = _lib.load().gdsm_nw_diff_batch
+    off = ctx.buffer(16).upload(np.zeros(2, np.uint64))
+    buf = ctx.buffer(16)
+    try:
+        assert fn(ctx.handle, buf.ptr, off.ptr, buf.ptr, off.ptr, 1, (1 << 20) + 1, buf.ptr,
+                  buf.ptr, buf.ptr) == -22
+        assert fn(ctx.handle, buf.ptr, off.ptr, buf.ptr, off.ptr, 0, 64, None, None, None) == 0
+        assert fn(ctx.handle, buf.ptr, off.ptr, buf.ptr, off.ptr, 1, 64, buf.ptr, buf.ptr,
+                  None) == -22
+    finally:
+        off.free()
+        buf.free()
 
 
 @pytest.mark.parametrize("name", ["c1", "cl", "dense", "edge"])
