@@ -1390,14 +1390,16 @@ __device__ __forceinline__ void store_chunks_wave(bool valid, uint8_t* dst, uint
 constexpr uint32_t kChunkMap = 512;  // chunks of one run batch mapped through LDS (else: search)
 
 // One staged window of the flat form: records j..k-1 of the wave's task (lane l's my_off / my_page:
-// record a + l's stream offset and page), their bytes [start, stop) in `win`. Returns 1 when a
+// record a + l's stream offset and page), their bytes [start, wend) in `win` (wend = stop, the
+// last record's end, unless the offsets are out of order). Returns 1 when a
 // record of the window is malformed (its runs are not written).
 template <int kNT>
 __device__ __forceinline__ uint32_t flat_window(uint8_t* __restrict__ target,
                                                 const uint32_t* __restrict__ win, uint4* ri,
                                                 uint4* rp, uint8_t* cm, uint64_t my_off,
                                                 uint32_t my_page, uint32_t j, uint32_t k,
-                                                uint64_t start, uint64_t stop) {
+                                                uint64_t start, uint64_t stop,
+                                                uint64_t wend) {
   const uint32_t lane = lane_id();
   uint32_t bad = 0;
   // ---- records: lane l = record j + l of the window
@@ -1408,8 +1410,8 @@ __device__ __forceinline__ uint32_t flat_window(uint8_t* __restrict__ target,
   const uint64_t o1n = __shfl(my_off, (int)min(r + 1, 63u), 64);
   const uint64_t o1 = (j + lane + 1 == k) ? stop : o1n;
   // offsets out of order (an unchecked caller stream) can put a record of the window outside
-  // [start, stop): it is malformed and writes nothing (its bytes are not in the window)
-  const bool outside = inrec && (o0 < start || o1 < o0 || o1 > stop);
+  // [start, wend): it is malformed and writes nothing (its bytes are not in the window)
+  const bool outside = inrec && (o0 < start || o1 < o0 || o1 > wend);
   const uint32_t rs = inrec && !outside ? (uint32_t)(o0 - start) : 0u;
   const uint32_t size = inrec && !outside ? (uint32_t)(o1 - o0) : 0u;
   uint32_t nr = size ? win[rs / 4] : 0u;
@@ -1524,7 +1526,7 @@ __device__ __forceinline__ uint32_t flat_window(uint8_t* __restrict__ target,
   return bad;
 }
 
-template <uint32_t kWin, bool kX4 = true, int kNT = 0>
+template <uint32_t kWin, bool kX4 = true, int kNT = 0, bool kScatter = false>
 __global__ __launch_bounds__(256) void apply_flat_kernel(uint8_t* __restrict__ target,
                                                          const uint32_t* __restrict__ ids,
                                                          uint64_t n,
@@ -1544,8 +1546,19 @@ __global__ __launch_bounds__(256) void apply_flat_kernel(uint8_t* __restrict__ t
   uint8_t* cm = cm_all[wave];
   const uint64_t ntask = (n + 63) / 64;
   uint32_t bad = 0, sink = 0;
-  for (uint64_t task = (uint64_t)blockIdx.x * 4 + wave; task < ntask;
-       task += (uint64_t)gridDim.x * 4) {
+  // kScatter: the tasks are taken in a scattered order (a multiplication by an odd constant
+  // modulo the next power of two, walked on until it lands below ntask: a bijection of the
+  // tasks), so the waves that run together write all over the arena instead of into neighbouring
+  // pages: word-sized writes into a 64 GiB arena measured 0.83x the time that way
+  // (profiles/scatter_probe_16M.txt, w8rand against w8)
+  const uint64_t tmask = ntask > 1 ? (~0ull >> __clzll(ntask - 1)) : 0ull;
+  for (uint64_t task0 = (uint64_t)blockIdx.x * 4 + wave; task0 < ntask;
+       task0 += (uint64_t)gridDim.x * 4) {
+    uint64_t task = task0;
+    if (kScatter) {
+      do task = (task * 0x9E3779B97F4A7C15ull) & tmask;
+      while (task >= ntask);
+    }
     const uint64_t a = task * 64;
     const uint32_t cnt = (uint32_t)min((uint64_t)64, n - a);
     const uint64_t my_off = rec_off[a + min(lane, cnt)];  // lane l: start of record a+l
@@ -1570,7 +1583,14 @@ __global__ __launch_bounds__(256) void apply_flat_kernel(uint8_t* __restrict__ t
         continue;
       }
       const uint64_t stop = (k == 64) ? end_off : lane_bcast64(my_off, k);
-      const uint32_t words = (uint32_t)((stop - start) >> 2);
+      // offsets out of order (an unchecked caller stream): a record of the window may end past
+      // `stop`; the window is staged up to the highest offset in it, so that the well-formed
+      // record before a misplaced offset keeps its bytes
+      uint64_t wend = stop;
+      const bool inw = lane > j && lane < k && (my_off - start) <= kWin;
+      if (__ballot(inw && my_off > stop))
+        wend = start + lane_bcast(wave_incl_max(inw ? (uint32_t)(my_off - start) : 0u), 63);
+      const uint32_t words = (uint32_t)((wend - start) >> 2);
       const uint32_t* src = reinterpret_cast<const uint32_t*>(data + start);
       typedef __attribute__((address_space(1))) void* gptr;
       typedef __attribute__((address_space(3))) void* lptr;
@@ -1599,7 +1619,7 @@ __global__ __launch_bounds__(256) void apply_flat_kernel(uint8_t* __restrict__ t
       __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the window has landed
       wave_lds_sync();
 
-      bad |= flat_window<kNT>(target, win, ri, rp, cm, my_off, my_page, j, k, start, stop);
+      bad |= flat_window<kNT>(target, win, ri, rp, cm, my_off, my_page, j, k, start, stop, wend);
       j = k;
     }
   }
@@ -1639,10 +1659,8 @@ static int diff_variant_from_env() {
 static std::atomic<int> g_diff_variant{diff_variant_from_env()};
 static int diff_variant() { return g_diff_variant.load(std::memory_order_relaxed); }
 // Apply geometry, gdsm_tune("apply_variant", v) or GDSM_APPLY_VARIANT=v (same output):
-//   0  default: long lists (> 16384 records) the flat form (apply_flat_kernel: the window's runs
-//      64 at a time, chunks spread over the wave) with a 4 KiB window filled 16 B per lane, whole
-//      aligned 8-B words stored nontemporally; short lists apply_kernel with 4 records per task
-//      and a 12 KiB window
+//   0  default: long lists (> 16384 records) the form of 8; short lists apply_kernel with 4
+//      records per task and a 12 KiB window
 //   1  long lists: apply_kernel (records row by row), 8 KiB window (round 2's default)
 //   2  long lists: apply_kernel, 4 KiB window
 //   3  long lists: flat form, 8 KiB window
@@ -1650,11 +1668,23 @@ static int diff_variant() { return g_diff_variant.load(std::memory_order_relaxed
 //   5  long lists: flat form, 4 KiB window filled by dword LDS-DMA (round 3's first default)
 //   6  long lists: flat form, whole chunks stored nontemporally too
 //   7  long lists: flat form, every store cached (round 3's first flat default)
+//   8  long lists: the flat form (apply_flat_kernel: the window's runs 64 at a time, chunks
+//      spread over the wave) with a 4 KiB window filled 16 B per lane, whole aligned 8-B words
+//      stored nontemporally, the 64-record tasks taken in a scattered order (3 to 7 take them in
+//      list order, as the default did before)
 // Same box, 4M pages: uniform 1 % 0.966 ms (7) -> 0.932 (0); clustered 1.058 (7), 1.065 (0),
 // 1.234 (6).
 // Same-box, 2M clustered pages (config-3 shard): 0.79 ms (1) -> 0.64 (2) -> 0.55 (0); config 2:
 // 0.250 -> 0.241 ms.
-constexpr int kApplyVariants = 8;
+// Scattered against list order (profiles/apply_onewin_ab.txt), in one process each pair: 16M
+// pages, uniform 1 %: 3.24 -> 2.64 ms, 3.36 -> 2.67, 3.76 -> 3.80; clustered: 4.45 -> 4.30,
+// 4.24 -> 3.69; 1M pages, uniform 1 %: 0.2365 -> 0.2384. The headline step, alternating
+// processes on three boxes: list order 24.42 / 24.88 / 24.87, 24.74 / 24.89 / 24.89 and 24.72 /
+// 24.74 / 24.63 ms, scattered 24.13 / 24.18 / 24.20, 23.95 / 23.96 / 24.35 and 23.99 / 24.00 /
+// 23.93 (the kernel's rocprof average 3.273 -> 2.750 ms). (A one-window form, a 5 KiB window
+// in the chunk map's LDS with partial chunks stored lane by lane, gained nothing: 3.132 ->
+// 3.128 ms at 16M uniform, and lost 6 % on clustered pages; it is not kept.)
+constexpr int kApplyVariants = 9;
 static int apply_variant_from_env() {
   const char* e = getenv("GDSM_APPLY_VARIANT");
   const int v = e ? atoi(e) : 0;
@@ -2214,7 +2244,7 @@ hipError_t launch_apply(uint8_t* target, const uint32_t* ids, uint64_t n,
     return hipGetLastError();
   }
   if (!short_list && (av == 0 || av >= 3)) {
-    auto kf = av == 0 ? apply_flat_kernel<4096, true, 1>
+    auto kf = av == 0 || av == 8 ? apply_flat_kernel<4096, true, 1, true>
               : av == 3 ? apply_flat_kernel<8192, true, 1>
               : av == 5 ? apply_flat_kernel<4096, false, 1>
               : av == 6 ? apply_flat_kernel<4096, true, 2>

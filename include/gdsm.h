@@ -662,7 +662,7 @@ int gdsm_dirty_scan_raw(const uint8_t* a, const uint8_t* b, const uint32_t* ids,
 
 const char* gdsm_version(void);
 /* Process-wide kernel-variant knobs for measurement (every value produces the same results):
- * "diff_variant" 0..8 (diff geometry), "apply_variant" 0..7, "diff_solo_max" 0..16 and
+ * "diff_variant" 0..8 (diff geometry), "apply_variant" 0..8, "diff_solo_max" 0..16 and
  * "diff_chain" 0..4 (short lists: one-workgroup / chained forms), "coh_variant" 0..2,
  * "coh_chain" 0|1 (small coherence batches without the zeroing launch), "coh_span" 1|2|4 (their
  * span, in 64-event chunks). Returns 0, or -EINVAL

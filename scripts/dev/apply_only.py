@@ -1,7 +1,11 @@
 """Apply kernel alone on one workload (re-applying the same stream is idempotent), for rocprofv3
 PMC passes and same-box A/B of apply variants (gdsm_tune "apply_variant").
 
-    APPLY_MODE=clustered APPLY_PAGES=2097152 APPLY_VARIANTS=0,1 python scripts/dev/apply_only.py"""
+    APPLY_MODE=clustered APPLY_PAGES=2097152 APPLY_VARIANTS=0,1 python scripts/dev/apply_only.py
+
+APPLY_MODE clustered (10 % of 64-B clusters) or uniform (1 % words), APPLY_PAGES, APPLY_VARIANTS (in
+this order within a round), APPLY_ROUNDS alternating rounds (3) of APPLY_REPS launches (10). One
+line per variant: the median of the rounds' ms per launch, then every round."""
 import os
 import statistics
 import sys
@@ -28,7 +32,7 @@ ctx.sync()
 total = runs.total()
 L = gdsm.lib()
 res = {}
-for rnd in range(3):
+for rnd in range(int(os.environ.get("APPLY_ROUNDS", 3))):
     for v in variants:
         assert L.gdsm_tune(b"apply_variant", v) == 0
         ctx.apply(runs)
@@ -50,5 +54,5 @@ ok = rc == 0 and chk.total() == 0
 for v, ts in res.items():
     ms = statistics.median(ts)
     print(f"apply_variant={v} {mode} n={n} stream={total} B: {ms:.4f} ms "
-          f"({2 * total / ms / 1e9:.0f} GB/s of stream read + payload written, approx) "
-          f"replica_ok={ok}", flush=True)
+          f"({2 * total / ms / 1e6:.0f} GB/s of stream read + payload written, approx) "
+          f"rounds={' '.join(f'{t:.4f}' for t in ts)} replica_ok={ok}", flush=True)

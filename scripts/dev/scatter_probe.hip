@@ -1,17 +1,21 @@
 // Scattered-write probe for the apply kernel's access pattern on gfx950 (not product code):
-// 1M pages x 5 dirty 8-B words per page (BASELINE config 2's 1 % word writes) written into a
-// 4 GiB REPLICA arena, followed by the diff-shaped read stream over two other 4 GiB arenas.
+// n pages (argument, default 1M) x 5 dirty 8-B words per page (BASELINE config 2's 1 % word
+// writes) written into an n x 4 KiB REPLICA arena, followed by the diff-shaped read stream over
+// two other arenas of that size (3 x 64 GiB at the north star's 16777216 pages).
 // Reports the write kernel's time and how much longer the following read stream takes than
 // after an empty kernel (the deferred write-back of the dirty lines), per write shape:
 //   w8      one lane per word, 8-B store (what apply does), pages in order
+//   w8nt    the same, stored nontemporally (what apply issues for whole aligned words)
 //   w8rand  the same words, pages in random order
 //   l64     the 64-B line holding the word stored whole (16 lanes x 4 B)
 //   l128    the 128-B line holding the word stored whole (32 lanes x 4 B)
 //   rmw64   the 64-B line read, the word merged in, the line stored whole
 //   hipcc --offload-arch=gfx950 -O3 scripts/dev/scatter_probe.hip -o scripts/dev/scatter_probe
+//   scripts/dev/scatter_probe [pages]
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <algorithm>
 #include <vector>
 
@@ -32,13 +36,16 @@ __device__ __forceinline__ void word_at(uint64_t w, uint64_t n, bool rnd, uint64
   off = (uint32_t)(mix(w * 131 + 5) % 512) * 8;
 }
 
-template <bool RND>
+template <bool RND, bool NT = false>
 __global__ void w8(uint8_t* __restrict__ rep, uint64_t n) {
   const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= n * kWordsPerPage) return;
   uint64_t p; uint32_t o;
   word_at(w, n, RND, p, o);
-  *reinterpret_cast<uint64_t*>(rep + p * 4096 + o) = w * 0x9E3779B97F4A7C15ull;
+  uint64_t* d = reinterpret_cast<uint64_t*>(rep + p * 4096 + o);
+  const uint64_t v = w * 0x9E3779B97F4A7C15ull;
+  if (NT) __builtin_nontemporal_store(v, d);
+  else *d = v;
 }
 
 template <int LINE>
@@ -89,8 +96,11 @@ __global__ __launch_bounds__(256) void rd_flat(const u32x4* __restrict__ a, cons
 
 typedef void (*WK)(uint8_t*, uint64_t);
 
-int main() {
-  const uint64_t n = 1 << 20, chunks = n * 256, words = n * kWordsPerPage;
+int main(int argc, char** argv) {
+  const uint64_t n = argc > 1 ? strtoull(argv[1], nullptr, 0) : 1ull << 20;
+  if (n == 0 || n > (1ull << 24)) { printf("pages: 1..16777216\n"); return 2; }
+  printf("pages %llu, words %llu\n", (unsigned long long)n, (unsigned long long)(n * kWordsPerPage));
+  const uint64_t chunks = n * 256, words = n * kWordsPerPage;
   u32x4 *a, *b;
   uint8_t* rep;
   uint32_t* out;
@@ -105,6 +115,7 @@ int main() {
   struct V { const char* name; WK k; uint64_t threads; };
   std::vector<V> vs = {{"nop   ", nop, 64},
                        {"w8    ", w8<false>, words},
+                       {"w8nt  ", w8<false, true>, words},
                        {"w8rand", w8<true>, words},
                        {"l64   ", wline<64>, words * 16},
                        {"l128  ", wline<128>, words * 32},
@@ -133,8 +144,9 @@ int main() {
   for (size_t v = 0; v < vs.size(); ++v) {
     std::sort(tw[v].begin(), tw[v].end());
     std::sort(tr[v].begin(), tr[v].end());
-    printf("%s write %.4f ms  following read %.4f ms  (sum %.4f)\n", vs[v].name, tw[v][R / 2],
-           tr[v][R / 2], tw[v][R / 2] + tr[v][R / 2]);
+    printf("%s write %.4f ms  following read %.4f ms  (sum %.4f)  read %.0f GB/s\n", vs[v].name,
+           tw[v][R / 2], tr[v][R / 2], tw[v][R / 2] + tr[v][R / 2],
+           (double)chunks * 32 / (tr[v][R / 2] * 1e6));
   }
   return 0;
 }
