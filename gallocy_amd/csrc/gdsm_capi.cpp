@@ -1045,26 +1045,25 @@ int gdsm_rounds(gdsm_ctx* data, gdsm_ctx* pt, uint32_t n_rounds, const uint64_t*
   const uint64_t gp_n = std::min<uint64_t>(std::max<uint64_t>((max_ev + 1023) / 1024, 1), 256);
   // small rounds (every round's workgroups fit one XCD, one per CU) run on one-XCD teams: a grid of
   // 8x the workgroups, the members being those on the first one's XCD (about 1 in 8), their
-  // hand-offs meeting in that XCD's L2. GDSM_ROUNDS_XCD=0 / 1 forces the choice (A/B runs).
-  const char* xe = getenv("GDSM_ROUNDS_XCD");  // (read per call: tests switch it)
-  const int xcd_env = xe && *xe ? (xe[0] == '1' ? 1 : 0) : -1;
-  const bool xcd = xcd_env == 1 || (xcd_env < 0 && gd_n <= 32 && gp_n <= 32);
+  // hand-offs meeting in that XCD's L2. The knob "rounds_xcd" = 0 / 1 forces the choice (A/B runs).
+  const int xcd_knob = gdsm::knob(gdsm::kRoundsXcd);
+  const bool xcd = xcd_knob == 1 || (xcd_knob < 0 && gd_n <= 32 && gp_n <= 32);
   const uint64_t gd_grid = xcd ? 8 * gd_n : gd_n, gp_grid = xcd ? 8 * gp_n : gp_n;
   // a page table and rounds this small fold on a few workgroups that keep slices of the table in
-  // LDS (no grid barrier, no gathers, no hand-off); GDSM_ROUNDS_LDS=0 / 1 forces the choice
-  const char* le = getenv("GDSM_ROUNDS_LDS");  // (read per call: tests switch it)
+  // LDS (no grid barrier, no gathers, no hand-off); the knob "rounds_lds" = 0 / 1 forces the choice
+  const int lds_knob = gdsm::knob(gdsm::kRoundsLds);
   // its workgroups: one per kRoundsLdsWGEvents of the largest round, and enough that every slice
-  // of the table fits (GDSM_ROUNDS_LDS_WG forces the count: A/B runs)
-  const char* lw = getenv("GDSM_ROUNDS_LDS_WG");
+  // of the table fits (the knob "rounds_lds_wg" > 0 forces the count: A/B runs)
+  const int lds_wg_knob = gdsm::knob(gdsm::kRoundsLdsWg);
   uint64_t lds_wg = std::max<uint64_t>(
       std::max<uint64_t>((max_ev + gdsm::kRoundsLdsWGEvents - 1) / gdsm::kRoundsLdsWGEvents, 1),
       (pt->n_pages + gdsm::kRoundsLdsPages - 1) / gdsm::kRoundsLdsPages);
-  if (lw && *lw) lds_wg = std::max<uint64_t>((uint64_t)atoll(lw), 1);
+  if (lds_wg_knob > 0) lds_wg = (uint64_t)lds_wg_knob;
   const bool lds_fits = lds_wg <= gdsm::kRoundsLdsMaxWGs &&
                         (pt->n_pages + lds_wg - 1) / lds_wg <= gdsm::kRoundsLdsPages &&
                         max_ev <= gdsm::kRoundsLdsEvents && n_rounds <= gdsm::kRoundsLdsRounds;
-  const bool lds = lds_fits && !(le && *le == '0');
-  if (le && *le == '1' && !lds_fits) return -EINVAL;
+  const bool lds = lds_fits && lds_knob != 0;
+  if (lds_knob == 1 && !lds_fits) return -EINVAL;
   if (gd_grid > resident_grid(gdsm::rounds_data_kernel_ptr(xcd)) ||
       (!lds && gp_grid > resident_grid(gdsm::rounds_fold_kernel_ptr(xcd))))
     return -EINVAL;

@@ -20,11 +20,6 @@
 #include "gdsm_common.h"
 #include "gdsm_launch.h"
 
-#include <stdlib.h>
-#include <string.h>
-
-#include <atomic>
-
 namespace gdsm {
 
 constexpr uint32_t kConst = 1u << 31;
@@ -116,49 +111,22 @@ __global__ __launch_bounds__(256) void coh_init_kernel(uint64_t* __restrict__ pt
 // has published its inclusive prefix, and every wave publishes only after its loads landed, so
 // the head's wave has read the word before anyone stores it. Page ids are taken from the low
 // dword (n_pages <= 2^28; any high-dword bit rejects the batch).
-// Events per lane: 32 (2048-event blocks). A -DGDSM_FOLD_K=16 build (1024-event blocks, 64 VGPRs
-// and 16 KiB of LDS per workgroup: 8 waves/SIMD instead of 5) is bit-exact and measured slower,
-// 3.18 / 3.03 ms against 2.42 / 2.43 (uniform / Zipf, same box): twice the blocks, twice the
-// per-block prologue, look-back and tail.
-#ifndef GDSM_FOLD_K
-#define GDSM_FOLD_K 32
-#endif
-// Issue priority (GDSM_FOLD_PRIO, default 5): bit 0 raises a wave's priority (s_setprio 3) from
-// its start until its block's event loads are issued and copied to LDS; bit 2 keeps it raised
-// until the page-table words of the lanes' first and last heads are requested too; bit 1 raises
-// it (2) from the look-back to the end. A wave that starts a block is the youngest on its SIMD,
-// so without the raise its loads queue behind the older waves' walks, and its whole block
-// starts late. Measured, same box, alternating (uniform / Zipf ms): 0: 2.41 / 2.42-2.43,
-// 1: 2.29-2.32 / 2.41-2.43, 5: 2.30-2.31 / 2.42-2.43, 2: 2.40-2.41 / 2.42-2.44, 3: 2.29-2.30.
-// GDSM_FOLD_PRE2 (default 1): the words of a lane's first GDSM_FOLD_PRE2 middle heads (its
-// second, third head when it has more) are loaded with the first and last heads' words, before
-// the walk, instead of inside it.
-#ifndef GDSM_FOLD_PRE2
-#define GDSM_FOLD_PRE2 1
-#endif
-#ifndef GDSM_FOLD_PRIO
-#define GDSM_FOLD_PRIO 5
-#endif
-// GDSM_FOLD_REGHEADS (whole blocks): events loaded as 128q + lane and 128q + 64 + lane (8-B
-// loads), their head flags taken in registers from the neighbouring lane's page, and two ballots
-// per 128 events written into the head masks of walk lanes 4q .. 4q + 3 (v_writelane) — the
-// heads pass over the LDS copy goes away. Bit-exact and slower, so off: without the heads pass the
-// walk's allocation grows to 111 VGPRs (4 waves/SIMD; held to 5 it spills): 2.42 / 2.50 ms
-// against 2.25 / 2.31 (uniform / Zipf, same box, alternating; profiles/r06_coh_regheads_ab.txt).
-#ifndef GDSM_FOLD_REGHEADS
-#define GDSM_FOLD_REGHEADS 0
-#endif
-// GDSM_FOLD_SPEC (whole blocks; 1: first and last heads, 2: the second head too): the heads'
-// page-table words guessed from the lane's first and last events and gathered before the heads
-// pass instead of after it (see the walk prologue). Bit-exact and slower, so off: the guesses
-// are live through the heads pass, which takes the fold to 102-106 VGPRs (4 waves/SIMD), or to
-// 96 with spills when held to 5 waves/SIMD; measured in that form (same box, alternating, 3
-// rounds): 2.34 / 2.47-2.49 ms against 2.27-2.28 / 2.34-2.35 (uniform / Zipf),
+// Events per lane: 32 (2048-event blocks). 16 per lane (8 waves/SIMD, twice the blocks) was tried,
+// slower, see DESIGN §4.
+// Issue priority: a wave raises its priority (s_setprio 3) from its start until its block's
+// events are in LDS and the page-table words of the lanes' first and last heads are requested. A
+// wave that starts a block is the youngest on its SIMD, so without the raise its loads queue
+// behind the older waves' walks, and its whole block starts late. Lowering it once the events
+// are in LDS, and a second raise from the look-back to the end, were tried, no faster, see
+// DESIGN §4.
+// The word of a lane's second head (its first middle head) is loaded with the first and last
+// heads' words, before the walk, instead of inside it. The third head's too was tried, slower
+// (4 waves/SIMD), see profiles/r03_coh_pre2_ab.txt.
+// Head masks taken in registers while the events load (no heads pass over the LDS copy) were
+// tried, slower, see DESIGN §0b / profiles/r06_coh_regheads_ab.txt.
+// The heads' words guessed and gathered before the heads pass were tried, slower, see DESIGN §0b /
 // profiles/r06_coh_spec_ab.txt.
-#ifndef GDSM_FOLD_SPEC
-#define GDSM_FOLD_SPEC 0
-#endif
-constexpr uint32_t kFK = GDSM_FOLD_K;       // events per lane (16 or 32: hm is one 32-bit mask)
+constexpr uint32_t kFK = 32;                // events per lane (hm is one 32-bit mask)
 constexpr uint32_t kFH = 16;                // of them held in registers at a time
 constexpr uint32_t kFBlock = 64 * kFK;
 constexpr uint32_t kHE = 0x10000u, kHW = 0x20000u, kPRE = 0x40000u, kHRead = 0xFFu;
@@ -166,13 +134,6 @@ constexpr uint32_t kKr = kHRead | kHW | kPRE;  // kept by a read miss
 constexpr uint64_t kFAgg = 1ull << 62, kFIncl = 2ull << 62, kFHead = 1ull << 61;
 constexpr uint32_t kFoldCtrs = 8;                   // workgroup ticket counters
 constexpr uint64_t kFoldStatus = kFoldCtrs * 32;    // u64 index of block 0's status granule
-
-// v_writelane_b32 as the compiler's intrinsic (no __builtin in this clang; it owns M0)
-extern "C" __device__ int coh_writelane(int val, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
-__device__ __forceinline__ uint2 ld_nt8(const uint64_t* p) {
-  const uint64_t v = __builtin_nontemporal_load(p);
-  return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
-}
 
 __device__ __forceinline__ uint32_t hit_seed(uint32_t w) {
   const uint32_t c = w & 0xFFu;
@@ -261,7 +222,7 @@ __device__ __forceinline__ void coh_fold_wave(uint64_t* __restrict__ pt, uint64_
   const uint32_t nv =
       kFull ? kFK : (uint32_t)min((uint64_t)kFK, g0 < n ? n - g0 : (uint64_t)0);
   COH_FSTAMP(0, __builtin_amdgcn_s_memtime());
-  if (GDSM_FOLD_PRIO & 1) __builtin_amdgcn_s_setprio(3);
+  __builtin_amdgcn_s_setprio(3);
   // ---- events: low dwords (page << 4 | node << 1 | rw) into the wave's LDS copy of the block;
   // every high-dword bit is an error. Coalesced 16-B loads (load q: events [128q, 128q + 128),
   // two per lane); each lane then reads its 32 consecutive events 16 at a time. (Loading a
@@ -271,62 +232,7 @@ __device__ __forceinline__ void coh_fold_wave(uint64_t* __restrict__ pt, uint64_
   typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
   uint32_t eagg = 0;
   bool early = false;
-  uint32_t hm_r = 0, dec_r = 0;  // GDSM_FOLD_REGHEADS: this lane's head mask, a page decreased
-  if (kVec && kFull && GDSM_FOLD_REGHEADS) {
-    // the page of the event before the block (uniform)
-    uint32_t pprev = (lo > 0 ? (uint32_t)ev[kM == 4 ? (lo_src ? lo_src - 1 : 0) : lo - 1] + padd : 0u) >> 4;
-    uint32_t ea = 0, eb = 0;  // events 1920 + lane and 1984 + lane
-    uint2 VA[kFBlock / 128], VB[kFBlock / 128];  // every load in flight at once
-#pragma unroll
-    for (uint32_t q = 0; q < kFBlock / 128; ++q) {
-      VA[q] = ld_nt8(ev + lo_src + 128 * q + lane);
-      VB[q] = ld_nt8(ev + lo_src + 128 * q + 64 + lane);
-    }
-#pragma unroll
-    for (uint32_t q = 0; q < kFBlock / 128; ++q) {
-      const uint2 va = VA[q], vb = VB[q];
-      hib |= va.y | vb.y;
-      const uint32_t xa = va.x + padd, xb = vb.x + padd;
-      tr[fold_slot(128 * q + lane)] = xa;
-      tr[fold_slot(128 * q + 64 + lane)] = xb;
-      const uint32_t pa = xa >> 4, pb = xb >> 4;
-      uint32_t qa = from_prev_lane(pa), qb = from_prev_lane(pb);
-      if (lane == 0) {
-        qa = pprev;
-        qb = lane_bcast(pa, 63);
-      }
-      pprev = lane_bcast(pb, 63);
-      const bool first = q == 0 && lo == 0 && lane == 0;  // the batch's first event
-      dec_r |= ((!first && pa < qa) || pb < qb) ? 1u : 0u;
-      asm volatile("" : "+v"(dec_r));  // now: sunk, it kept every chunk's pages live
-      const uint64_t Ma = __ballot(first || pa != qa), Mb = __ballot(pb != qb);
-      hm_r = (uint32_t)coh_writelane((int)(uint32_t)Ma, (int)(4 * q), (int)hm_r);
-      hm_r = (uint32_t)coh_writelane((int)(uint32_t)(Ma >> 32), (int)(4 * q + 1), (int)hm_r);
-      hm_r = (uint32_t)coh_writelane((int)(uint32_t)Mb, (int)(4 * q + 2), (int)hm_r);
-      hm_r = (uint32_t)coh_writelane((int)(uint32_t)(Mb >> 32), (int)(4 * q + 3), (int)hm_r);
-      if (q == kFBlock / 128 - 1) {
-        ea = xa;
-        eb = xb;
-      }
-    }
-    // ---- early aggregate (as below, in this layout: a = event 1920 + lane, b = 1984 + lane)
-    const uint64_t bwb = __ballot((eb & 1u) != 0), bwa = __ballot((ea & 1u) != 0);
-    if (kM == 0 && b > 0 && (bwa | bwb)) {
-      const bool inb = bwb != 0;
-      const uint32_t Lw = 63u - (uint32_t)__builtin_clzll(inb ? bwb : bwa);
-      const uint32_t xw = inb ? lane_bcast(eb, (int)Lw) : lane_bcast(ea, (int)Lw);
-      const uint32_t wi = (inb ? 64u : 0u) + Lw;
-      if ((xw >> 4) == (lane_bcast(eb, 63) >> 4)) {
-        const uint32_t r = (lane > wi ? 1u << ((ea >> 1) & 7u) : 0u) |
-                           (64u + lane > wi ? 1u << ((eb >> 1) & 7u) : 0u);
-        uint32_t R = 0;
-#pragma unroll
-        for (uint32_t nd = 0; nd < 8; ++nd) R |= __ballot((r >> nd) & 1u) ? 1u << nd : 0u;
-        eagg = tcompose(kConst | wr_word(xw), R);
-        early = true;
-      }
-    }
-  } else if (kVec && kFull) {
+  if (kVec && kFull) {
     uint32_t e0 = 0, e1 = 0;  // events 1920 + 2 * lane and the one after it
 #pragma unroll
     for (uint32_t q = 0; q < kFBlock / 128; ++q) {
@@ -368,7 +274,6 @@ __device__ __forceinline__ void coh_fold_wave(uint64_t* __restrict__ pt, uint64_
   }
   wave_lds_sync();
   COH_FSTAMP(1, __builtin_amdgcn_s_memtime());
-  if ((GDSM_FOLD_PRIO & 5) == 1) __builtin_amdgcn_s_setprio(0);
   const uint32_t xprev_w = lo > 0 ? (uint32_t)ev[kM == 4 ? (lo_src ? lo_src - 1 : 0) : lo - 1] + padd
                                   : 0u;  // uniform
   const bool has_next = lo + kFBlock < n;
@@ -378,40 +283,14 @@ __device__ __forceinline__ void coh_fold_wave(uint64_t* __restrict__ pt, uint64_
   uint32_t xp = from_prev_lane(tr[fold_slot(kFK * lane + kFK - 1)]);
   if (lane == 0) xp = xprev_w;
   const bool batch_first = lo == 0 && lane == 0;
-#if GDSM_FOLD_SPEC
-  // ---- the page-table words of the lane's heads, guessed and gathered BEFORE the heads pass, so
-  // their latency hides behind it: the lane's last head is the page of its last event (whenever
-  // the lane has a head), its first head the page of its first event or, when that event
-  // continues an earlier segment, the next page (right whenever the batch's pages are dense, as
-  // config 4's are), its second head the page after the first. A wrong guess is loaded again
-  // after the heads pass; a guessed word that is not one of the lane's heads is never used
-  // (another wave may be storing it).
-  uint64_t Wl_s = 0, Wf_s = 0, Ws_s = 0;
-  uint32_t pf_s = 0;
-  if (kFull) {
-    const uint32_t pg0 = tr[fold_slot(kFK * lane)] >> 4;
-    pf_s = (batch_first || pg0 != (xp >> 4)) ? pg0 : pg0 + 1u;
-    const uint32_t pl_s = xlast >> 4;
-    if (pl_s < n_pages) Wl_s = pt[pl_s];
-    if (pf_s < pl_s && pf_s < n_pages) Wf_s = pt[pf_s];
-#if GDSM_FOLD_SPEC > 1
-    if (pf_s + 1u < pl_s && pf_s + 1u < n_pages) Ws_s = pt[pf_s + 1u];
-#endif
-  }
-#endif
 
   // ---- heads (a new page), validity. (Sortedness inside a lane is checked where the walk meets
   // a head; the first / last head events are read back from LDS.)
   uint32_t X[kFH];
   uint32_t hm = 0;
   uint32_t bad = hib ? 1u : 0u;
-  constexpr bool kRegHeads = kVec && kFull && GDSM_FOLD_REGHEADS;
-  if (kRegHeads) {
-    hm = hm_r;
-    if (dec_r) bad = 1;
-  }
 #pragma unroll
-  for (uint32_t h = 0; h < (kRegHeads ? 0u : kFK / kFH); ++h) {
+  for (uint32_t h = 0; h < kFK / kFH; ++h) {
     fold_half(tr, lane, h, X);
 #pragma unroll
     for (uint32_t j = 0; j < kFH; ++j) {
@@ -430,7 +309,7 @@ __device__ __forceinline__ void coh_fold_wave(uint64_t* __restrict__ pt, uint64_
     }
     xp = X[kFH - 1];
   }
-  if (kFull && !kRegHeads) hm = __brev(hm) >> (32u - kFK);
+  if (kFull) hm = __brev(hm) >> (32u - kFK);
   const uint32_t hc = (uint32_t)__popc(hm);
   uint32_t xf = 0, xl = 0;  // the lane's first and last head events
   if (hc) {
@@ -449,46 +328,22 @@ __device__ __forceinline__ void coh_fold_wave(uint64_t* __restrict__ pt, uint64_
   if (!kFull && nv > 0 && g0 + nv == n) last_end = true;
 
   COH_FSTAMP(6, __builtin_amdgcn_s_memtime());
-  // ---- page-table words of the lane's last and first heads (one gathered load each)
-  uint64_t Wl = 0, Wf = 0, Ws = 0, Wt = 0;  // last, first, second, third heads (others: walk)
-#if GDSM_FOLD_SPEC
-  if (kFull) {  // the guesses above, and a load where one missed
-    const uint32_t pf = xf >> 4;
-    Wl = Wl_s;  // (pages of the lane's last head and last event are equal)
-    Wf = Wf_s;
-    if (hc > 1 && pf != pf_s && pf < n_pages) Wf = pt[pf];
-    if (GDSM_FOLD_PRE2 && hc > 2) {
-      const uint32_t h2 = hm & (hm - 1u);
-      const uint32_t p2 = tr[fold_slot(kFK * lane + (uint32_t)__builtin_ctz(h2))] >> 4;
-      Ws = Ws_s;
-      if ((GDSM_FOLD_SPEC < 2 || p2 != pf_s + 1u) && p2 < n_pages) Ws = pt[p2];
-      if (GDSM_FOLD_PRE2 > 1 && hc > 3) {
-        const uint32_t h3 = h2 & (h2 - 1u);
-        const uint32_t p3 = tr[fold_slot(kFK * lane + (uint32_t)__builtin_ctz(h3))] >> 4;
-        if (p3 < n_pages) Wt = pt[p3];
-      }
-    }
-  } else
-#endif
+  // ---- page-table words of the lane's last, first and second heads (one gathered load each)
+  uint64_t Wl = 0, Wf = 0, Ws = 0;  // (further middle heads: loaded in the walk)
   {
     const uint32_t pl = xl >> 4, pf = xf >> 4;
     if (hc && pl < n_pages) Wl = pt[pl];
     if (hc > 1 && pf < n_pages) Wf = pt[pf];
-    if (GDSM_FOLD_PRE2 && hc > 2) {  // a middle head: its page lies inside this lane
+    if (hc > 2) {  // a middle head: its page lies inside this lane
       const uint32_t h2 = hm & (hm - 1u);
       const uint32_t p2 = tr[fold_slot(kFK * lane + (uint32_t)__builtin_ctz(h2))] >> 4;
       if (p2 < n_pages) Ws = pt[p2];
-      if (GDSM_FOLD_PRE2 > 1 && hc > 3) {
-        const uint32_t h3 = h2 & (h2 - 1u);
-        const uint32_t p3 = tr[fold_slot(kFK * lane + (uint32_t)__builtin_ctz(h3))] >> 4;
-        if (p3 < n_pages) Wt = pt[p3];
-      }
     }
   }
   const uint32_t Bl = (uint32_t)Wl & 0x7FFFFu, Bfl = (uint32_t)(Wl >> 32);
   const uint32_t Hl = hit_seed(Bl), Ol = ((Bl >> 8) & 0xFFu) << 1;
-  if ((GDSM_FOLD_PRIO & 5) == 5) __builtin_amdgcn_s_setprio(0);
-  asm volatile("" : "+v"(Wf), "+v"(Ws), "+v"(Wt));  // waited for here, not inside the walk
+  __builtin_amdgcn_s_setprio(0);
+  asm volatile("" : "+v"(Wf), "+v"(Ws));  // waited for here, not inside the walk
 #ifdef GDSM_COH_STAMPS
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
   COH_FSTAMP(7, __builtin_amdgcn_s_memtime());
@@ -560,16 +415,13 @@ __device__ __forceinline__ void coh_fold_wave(uint64_t* __restrict__ pt, uint64_
             B = Bl;
             Bfo = Bfl;
           } else {
-            // the first head's word was loaded (and waited for) with the last head's, before the
-            // walk; a middle head (lanes with >= 3 heads) loads its word here. A word prefetched
-            // one head ahead instead made every head step wait: the wave's one vmcnt counter also
-            // counts the walk's stores, and some lane is at a head at most steps.
-            if (GDSM_FOLD_PRE2 && hs == 1) {
+            // the first and second heads' words were loaded (and waited for) with the last head's,
+            // before the walk; a later middle head (lanes with >= 4 heads) loads its word here. A
+            // word prefetched one head ahead instead made every head step wait: the wave's one
+            // vmcnt counter also counts the walk's stores, and some lane is at a head at most steps.
+            if (hs == 1) {
               B = (uint32_t)Ws & 0x7FFFFu;
               Bfo = (uint32_t)(Ws >> 32);
-            } else if (GDSM_FOLD_PRE2 > 1 && hs == 2) {
-              B = (uint32_t)Wt & 0x7FFFFu;
-              Bfo = (uint32_t)(Wt >> 32);
             } else if (hs != 0) {
               const uint32_t pg = x >> 4;  // a page >= n_pages fails the batch (clamped load)
               const uint64_t w = pt[pg < n_pages ? pg : 0u];
@@ -655,7 +507,6 @@ __device__ __forceinline__ void coh_fold_wave(uint64_t* __restrict__ pt, uint64_
   const bool ordered = kM != 3 &&
                        __ballot(hasD && (__ballot(hc != 0) & ((1ull << lane) - 1ull)) == 0) != 0;
   uint32_t carry = 0;
-  if (GDSM_FOLD_PRIO & 2) __builtin_amdgcn_s_setprio(2);
 #ifdef GDSM_COH_STAMPS
   uint32_t lb_rounds = 0;
 #endif
@@ -794,16 +645,10 @@ __device__ __forceinline__ void coh_fold_wave(uint64_t* __restrict__ pt, uint64_
   COH_FSTAMP(4, __builtin_amdgcn_s_memtime());
 }
 
-// Waves per workgroup (GDSM_FOLD_WAVES, 1, 2 or 4; default 4). LDS is held by a workgroup until
-// its last wave ends, so a four-wave workgroup keeps its 32 KiB after its earlier waves' blocks are
-// done; smaller workgroups free it sooner but measured slower (config 4, same box, alternating,
-// 2 rounds: 1 wave 2.75-2.77 / 2.62 ms, 2 waves 2.51 / 2.40, 4 waves 2.27-2.28 / 2.34 uniform /
-// Zipf; bit-exact, profiles/r06_coh_wg_ab.txt).
-#ifndef GDSM_FOLD_WAVES
-#define GDSM_FOLD_WAVES 4
-#endif
-constexpr uint32_t kFoldWaves = GDSM_FOLD_WAVES;
-static_assert(kFoldWaves == 1 || kFoldWaves == 2 || kFoldWaves == 4, "fold workgroup");
+// Waves per workgroup. LDS is held by a workgroup until its last wave ends; one- and two-wave
+// workgroups, which free it sooner, were tried, slower, see DESIGN §0b /
+// profiles/r06_coh_wg_ab.txt.
+constexpr uint32_t kFoldWaves = 4;
 
 // kFull: the batch's whole blocks, one ticket per workgroup (tickets are drawn in dispatch
 // order, so a wave only ever waits for running waves); otherwise the single trailing partial
@@ -1728,7 +1573,7 @@ __global__ __launch_bounds__(256) void gen_events_kernel(uint64_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------- launchers
-// Coherence variant (gdsm_tune "coh_variant" or GDSM_COH_VARIANT): 0 (default) = automatic: the
+// Coherence variant (the knob "coh_variant", kCohVariant): 0 (default) = automatic: the
 // streaming fold with 256-event spans up to kCohSmall events, the single-pass fold
 // (coh_fold_kernel) beyond; 1 = the streaming fold with 4096-event spans at every size; 2 = the
 // single-pass fold at every size. All write the same page table and totals
@@ -1737,45 +1582,11 @@ __global__ __launch_bounds__(256) void gen_events_kernel(uint64_t* __restrict__ 
 // without its look-back / without the ordered look-back, and 7 = with its events read from a hot
 // 64 MB window (coh_fold_wave kM 4). (1-3, the round-2 four-pass path, were
 // removed in round 4; its last version is in git history, commit 585a356.)
-#ifdef GDSM_MEASURE
-constexpr int kCohVariants = 8;
-static bool coh_variant_ok(int v) { return v <= 2 || (v >= 4 && v < kCohVariants); }
-#else
-static bool coh_variant_ok(int v) { return v >= 0 && v <= 2; }
-#endif
-static int coh_variant_from_env() {
-  const char* e = getenv("GDSM_COH_VARIANT");
-  const int v = e ? atoi(e) : 0;
-  return coh_variant_ok(v) ? v : 0;
-}
-static std::atomic<int> g_coh_variant{coh_variant_from_env()};
 // Small batches of a context outside graph capture: the chained one-launch form (CohChain) unless
-// gdsm_tune("coh_chain", 0) or GDSM_COH_CHAIN=0 at load (then the zeroing launch before the fold).
-static std::atomic<int> g_coh_chain{getenv("GDSM_COH_CHAIN") && atoi(getenv("GDSM_COH_CHAIN")) == 0 ? 0 : 1};
-// the chained fold's span (gdsm_tune("coh_span", 1 | 2 | 4) 64-event chunks, GDSM_COH_SPAN).
-// Config 5, same box, rounds/s, span 4 / 2 / 1 (and 8, not kept): 4 nodes 93.6k / 95.4k / 85.0k
-// (71.6k); 8 nodes 83.1k / 73.8k / 60.8k (66.3k); 1 node 94.3k / 96.2k (71.2k).
-static int coh_span_from_env() {
-  const char* e = getenv("GDSM_COH_SPAN");
-  const int v = e ? atoi(e) : 4;
-  return (v == 1 || v == 2 || v == 4) ? v : 4;
-}
-static std::atomic<int> g_coh_span{coh_span_from_env()};
-int coh_tune(const char* key, int64_t value) {
-  if (!strcmp(key, "coh_span") && (value == 1 || value == 2 || value == 4)) {
-    g_coh_span.store((int)value, std::memory_order_relaxed);
-    return 0;
-  }
-  if (!strcmp(key, "coh_chain") && (value == 0 || value == 1)) {
-    g_coh_chain.store((int)value, std::memory_order_relaxed);
-    return 0;
-  }
-  if (!strcmp(key, "coh_variant") && value >= 0 && value < 8 && coh_variant_ok((int)value)) {
-    g_coh_variant.store((int)value, std::memory_order_relaxed);
-    return 0;
-  }
-  return -1;
-}
+// the knob "coh_chain" is 0 (then the zeroing launch before the fold). The chained fold's span is
+// the knob "coh_span" (1 | 2 | 4 64-event chunks). Config 5, same box, rounds/s, span 4 / 2 / 1
+// (and 8, not kept): 4 nodes 93.6k / 95.4k / 85.0k (71.6k); 8 nodes 83.1k / 73.8k / 60.8k
+// (66.3k); 1 node 94.3k / 96.2k (71.2k).
 
 static inline uint64_t fold_blocks(uint64_t n) { return (n + kFBlock - 1) / kFBlock; }
 
@@ -1809,17 +1620,17 @@ hipError_t launch_coherence(uint64_t* pt, uint64_t n_pages, uint32_t n_nodes,
                             const uint64_t* events, uint64_t n_events, uint64_t* totals,
                             uint8_t* ws, uint64_t ws_bytes, uint32_t* err, hipStream_t s,
                             Prof* prof, CohChainState* chain) {
-  const int cv = g_coh_variant.load(std::memory_order_relaxed);
+  const int cv = knob(kCohVariant);
   const bool small = cv == 0 && n_events <= kCohSmall;
   if (n_events == 0) return hipMemsetAsync(totals, 0, 10 * sizeof(uint64_t), s);
-  if (small && chain && chain->ws && g_coh_chain.load(std::memory_order_relaxed)) {
+  if (small && chain && chain->ws && knob(kCohChain)) {
     // one launch: epoch-tagged granules, counters and totals row the previous launch zeroed
     if (chain->epoch == 0) {
       const hipError_t e = hipMemsetAsync(chain->ws, 0, coh_chain_bytes(), s);
       if (e != hipSuccess) return e;
       chain->epoch = 1;
     }
-    const uint32_t sc = (uint32_t)g_coh_span.load(std::memory_order_relaxed);  // chunks per span
+    const uint32_t sc = (uint32_t)knob(kCohSpan);  // chunks per span
     const uint64_t span = 64ull * sc;
     const uint64_t ns = (n_events + span - 1) / span, full = n_events / span;
     ProfScope ps(prof, GDSM_PROF_COH_FOLD, s);

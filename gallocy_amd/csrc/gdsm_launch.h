@@ -9,9 +9,27 @@ namespace gdsm {
 
 // Workspace of one diff of n list entries (ticket counter + one look-back granule per unit).
 uint64_t diff_workspace_bytes(uint64_t n);
-// Kernel variant knobs (see gdsm_tune); returns -1 for an unknown key.
+// Tuning knobs (gdsm_tune.cpp: one table row each, with its key, environment variable, accepted
+// values and default). tune returns -1 for an unknown key or a value the knob does not accept.
+enum Knob {
+  kDiffVariant,
+  kApplyVariant,
+  kDiffSoloMax,
+  kDiffChain,
+  kCohVariant,
+  kCohChain,
+  kCohSpan,
+  kRoundsXcd,
+  kRoundsLds,
+  kRoundsLdsWg,
+#ifdef GDSM_MEASURE
+  kDiffSkip,  // the chained release's kSkip
+#endif
+  kKnobs
+};
+int knob(Knob k);
 int tune(const char* key, int64_t value);
-int coh_tune(const char* key, int64_t value);
+constexpr uint32_t kSoloUnits = 16;  // pages of the one-workgroup release (gdsm_pages.hip, kSolo)
 
 hipError_t launch_gen_pages(uint8_t* twin, uint8_t* cur, uint8_t* replica, uint64_t n,
                             uint64_t first_global, uint64_t stride, uint64_t seed, int mode,

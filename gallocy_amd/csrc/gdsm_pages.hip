@@ -15,11 +15,6 @@
 #include "gdsm_launch.h"
 #include "gdsm_record.h"
 
-#include <stdlib.h>
-#include <string.h>
-
-#include <atomic>
-
 namespace gdsm {
 
 // ------------------------------------------------------------------------- synthetic pages
@@ -508,7 +503,7 @@ constexpr uint32_t kSpillWGs = 1280;  // > the workgroups of this kernel one MI3
 // unit, no ticket and no workspace. The exclusive offsets come from the waves' totals through LDS
 // and one barrier instead of the look-back, and the caller's id lists are guarded in the kernel
 // (g, as diff_prep_kernel does), so the release is this one launch (config 5's rounds).
-constexpr uint32_t kSoloUnits = 16;
+// (kSoloUnits: gdsm_launch.h)
 
 // A re-twin store may go to page pj: not the guard page, where every out-of-range entry of a
 // checked list points (those workgroups would write the guard page's TWIN while others read it,
@@ -1628,7 +1623,7 @@ __global__ __launch_bounds__(256) void apply_flat_kernel(uint8_t* __restrict__ t
 }
 
 // ------------------------------------------------------------------------- launchers
-// Diff geometry, gdsm_tune("diff_variant", v) or GDSM_DIFF_VARIANT=v; every variant writes the
+// Diff geometry, the knob "diff_variant" (kDiffVariant); every variant writes the
 // same canonical stream (tests/test_gpu_pages.py checks each):
 //   0  automatic (default): 2 pages per wave for short lists (n <= 32768: a wave walks its
 //      pages one after the other, so a few dozen pages must not share one wave); longer lists by
@@ -1651,14 +1646,8 @@ __global__ __launch_bounds__(256) void apply_flat_kernel(uint8_t* __restrict__ t
 //      capture: the one-workgroup kSolo launch up to diff_solo_max pages, the chained grid launch
 //      (kChain, no zeroing launch) beyond; otherwise kSolo up to kSoloUnits pages
 // Measurement-only kernels (invalid output) are not part of the library.
-static int diff_variant_from_env() {
-  const char* e = getenv("GDSM_DIFF_VARIANT");
-  const int v = e ? atoi(e) : 0;
-  return (v >= 0 && v <= 8) ? v : 0;
-}
-static std::atomic<int> g_diff_variant{diff_variant_from_env()};
-static int diff_variant() { return g_diff_variant.load(std::memory_order_relaxed); }
-// Apply geometry, gdsm_tune("apply_variant", v) or GDSM_APPLY_VARIANT=v (same output):
+static int diff_variant() { return knob(kDiffVariant); }
+// Apply geometry, the knob "apply_variant" (kApplyVariant; same output):
 //   0  default: long lists (> 16384 records) the form of 8; short lists apply_kernel with 4
 //      records per task and a 12 KiB window
 //   1  long lists: apply_kernel (records row by row), 8 KiB window (round 2's default)
@@ -1684,14 +1673,7 @@ static int diff_variant() { return g_diff_variant.load(std::memory_order_relaxed
 // 23.93 (the kernel's rocprof average 3.273 -> 2.750 ms). (A one-window form, a 5 KiB window
 // in the chunk map's LDS with partial chunks stored lane by lane, gained nothing: 3.132 ->
 // 3.128 ms at 16M uniform, and lost 6 % on clustered pages; it is not kept.)
-constexpr int kApplyVariants = 9;
-static int apply_variant_from_env() {
-  const char* e = getenv("GDSM_APPLY_VARIANT");
-  const int v = e ? atoi(e) : 0;
-  return (v >= 0 && v < kApplyVariants) ? v : 0;
-}
-static std::atomic<int> g_apply_variant{apply_variant_from_env()};
-// Short lists of one-page units (variant 8), gdsm_tune("diff_solo_max", k) and ("diff_chain", c):
+// Short lists of one-page units (variant 8), the knobs "diff_solo_max" = k and "diff_chain" = c:
 // up to k units the one-workgroup kSolo launch, beyond it a chained launch when the context
 // offers its DiffChain: c = 1 / 4: diff_single_kernel<..., kChainW> with 1 / 4 waves (pages) per
 // workgroup, c = 3: release_page_kernel (a page per four-wave workgroup), c = 2 (default):
@@ -1702,46 +1684,7 @@ static std::atomic<int> g_apply_variant{apply_variant_from_env()};
 // pages per workgroup 12.5) / 13.2 / 8.5; m = 2048 four per workgroup 30.7, page per workgroup
 // 45.1. Default k = 0: the one-workgroup form (up to kSoloUnits pages) serves graph capture,
 // which has no chain, and callers without a context.
-constexpr int kSoloDefault = 0;
-// (also GDSM_DIFF_SOLO_MAX / GDSM_DIFF_CHAIN at load)
-static int env_int(const char* name, int lo, int hi, int dflt) {
-  const char* e = getenv(name);
-  const int v = e ? atoi(e) : dflt;
-  return (e && v >= lo && v <= hi) ? v : dflt;
-}
-static std::atomic<int> g_solo_max{env_int("GDSM_DIFF_SOLO_MAX", 0, (int)kSoloUnits, kSoloDefault)};
 constexpr uint64_t kChainPerPage = 512;
-static std::atomic<int> g_chain{env_int("GDSM_DIFF_CHAIN", 0, 4, 2)};
-#ifdef GDSM_MEASURE
-static std::atomic<int> g_diff_skip{0};  // the chained release's kSkip (measurement builds)
-#endif
-
-
-int tune(const char* key, int64_t value) {
-  if (!strcmp(key, "diff_variant") && value >= 0 && value <= 8) {
-    g_diff_variant.store((int)value, std::memory_order_relaxed);
-    return 0;
-  }
-  if (!strcmp(key, "diff_solo_max") && value >= 0 && value <= (int64_t)kSoloUnits) {
-    g_solo_max.store((int)value, std::memory_order_relaxed);
-    return 0;
-  }
-#ifdef GDSM_MEASURE
-  if (!strcmp(key, "diff_skip") && value >= 0 && value < 64) {
-    g_diff_skip.store((int)value, std::memory_order_relaxed);
-    return 0;
-  }
-#endif
-  if (!strcmp(key, "diff_chain") && value >= 0 && value <= 4) {
-    g_chain.store((int)value, std::memory_order_relaxed);
-    return 0;
-  }
-  if (!strcmp(key, "apply_variant") && value >= 0 && value < kApplyVariants) {
-    g_apply_variant.store((int)value, std::memory_order_relaxed);
-    return 0;
-  }
-  return coh_tune(key, value);
-}
 
 // Single-pass diff workspace: the ticket counter and one status granule per unit of the
 // smallest geometry that n may take (2 pages up to kDiffShort, else 16), then the spill pool of
@@ -2103,9 +2046,8 @@ static hipError_t launch_diff_impl(const uint8_t* twin, const uint8_t* cur, cons
   // short lists: the chained launch (when the context offers it) from solo_max + 1 units, the
   // one-workgroup launch below (up to kSoloUnits without the chain)
   const bool chain_ok = v == 8 && sp.G == 1 && chain && chain->ws && nunits <= kDiffChainUnits &&
-                        g_chain.load(std::memory_order_relaxed);
-  const uint64_t solo_max =
-      chain_ok ? (uint64_t)g_solo_max.load(std::memory_order_relaxed) : (uint64_t)kSoloUnits;
+                        knob(kDiffChain);
+  const uint64_t solo_max = chain_ok ? (uint64_t)knob(kDiffSoloMax) : (uint64_t)kSoloUnits;
   if (v == 8 && sp.G == 1 && nunits <= solo_max) {
     // one workgroup, no workspace: the caller's lists are guarded by the kernel itself
     const IdGuard g = guard ? *guard : IdGuard{};
@@ -2128,7 +2070,7 @@ static hipError_t launch_diff_impl(const uint8_t* twin, const uint8_t* cur, cons
     sp.epoch = chain->epoch;
     const IdGuard g = guard ? *guard : IdGuard{};
     ProfScope ps(prof, GDSM_PROF_DIFF, s);
-    const int cw = g_chain.load(std::memory_order_relaxed);
+    const int cw = knob(kDiffChain);
     if (cw == 3 || (cw == 2 && nunits <= kChainPerPage)) {  // a page per four-wave workgroup
       auto kp = retwin ? (target ? release_page_kernel<true, true> : release_page_kernel<false, true>)
                        : (target ? release_page_kernel<true, false> : release_page_kernel<false, false>);
@@ -2140,8 +2082,8 @@ static hipError_t launch_diff_impl(const uint8_t* twin, const uint8_t* cur, cons
     }
     const uint32_t W = cw == 1 ? 1 : 4;  // waves per workgroup
 #ifdef GDSM_MEASURE
-    if (g_diff_skip.load(std::memory_order_relaxed) && retwin && target && W == 1) {
-      const int k = g_diff_skip.load(std::memory_order_relaxed);
+    if (knob(kDiffSkip) && retwin && target && W == 1) {
+      const int k = knob(kDiffSkip);
       auto km = k == 1   ? diff_single_kernel<1, 8192, 4, true, 0, false, true, 1, 1>
                 : k == 2  ? diff_single_kernel<1, 8192, 4, true, 0, false, true, 1, 2>
                 : k == 4  ? diff_single_kernel<1, 8192, 4, true, 0, false, true, 1, 4>
@@ -2237,7 +2179,7 @@ hipError_t launch_apply(uint8_t* target, const uint32_t* ids, uint64_t n,
   // few dense records are spread over waves instead of queueing in one
   const bool short_list = n <= 16384;
   const uint32_t per_task = short_list ? 4u : 64u;
-  const int av = g_apply_variant.load(std::memory_order_relaxed);
+  const int av = knob(kApplyVariant);
   if (n <= kApplyTiny && av == 0) {
     hipLaunchKernelGGL(apply_tiny_kernel<0>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s,
                        target, ids, n, rec_off, data, err);

@@ -661,12 +661,22 @@ int gdsm_dirty_scan_raw(const uint8_t* a, const uint8_t* b, const uint32_t* ids,
                         void* workspace, uint64_t workspace_bytes, void* stream);
 
 const char* gdsm_version(void);
-/* Process-wide kernel-variant knobs for measurement (every value produces the same results):
- * "diff_variant" 0..8 (diff geometry), "apply_variant" 0..8, "diff_solo_max" 0..16 and
- * "diff_chain" 0..4 (short lists: one-workgroup / chained forms), "coh_variant" 0..2,
- * "coh_chain" 0|1 (small coherence batches without the zeroing launch), "coh_span" 1|2|4 (their
- * span, in 64-event chunks). Returns 0, or -EINVAL
- * for an unknown key or value. */
+/* Process-wide knobs that choose a kernel variant or launch form, for measurement and tests (every
+ * value produces the same results). Key, accepted values, (default):
+ *   "diff_variant"   0..8 (0)    diff geometry
+ *   "apply_variant"  0..8 (0)    apply geometry
+ *   "diff_solo_max"  0..16 (0)   short lists: pages up to which the one-workgroup form is taken
+ *   "diff_chain"     0..4 (2)    short lists: the chained (zero-free) form
+ *   "coh_variant"    0..2 (0)    automatic / streaming fold / single-pass fold
+ *   "coh_chain"      0|1 (1)     small coherence batches without the zeroing launch
+ *   "coh_span"       1|2|4 (4)   their span, in 64-event chunks
+ *   "rounds_xcd"     -1|0|1 (-1) gdsm_rounds: automatic / the whole grid / a one-XCD team
+ *   "rounds_lds"     -1|0|1 (-1) gdsm_rounds' page-table side: automatic / the persistent grid /
+ *                                LDS slices (1 where they do not fit: gdsm_rounds returns -EINVAL)
+ *   "rounds_lds_wg"  0..16 (0)   workgroups of the LDS form, 0 = automatic
+ * Each key is also the environment variable GDSM_<KEY> (upper case), read once when the library
+ * loads; a value that is not accepted there leaves the default. Returns 0, or -EINVAL for an
+ * unknown key or a value that is not accepted. */
 int gdsm_tune(const char* key, int64_t value);
 /* Test hook: the nth next growth of one of ctx's internal workspaces fails with -ENOMEM (0 = off).
  * Used to show that a collective call refuses on every rank together when one rank fails. */

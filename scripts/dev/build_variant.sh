@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B build of libgdsm with extra compile flags into gallocy_amd/<dir>/ (not product code):
-#   scripts/dev/build_variant.sh lib_v1 -DGDSM_FOLD_PRIO=1
+#   scripts/dev/build_variant.sh lib_st -DGDSM_COH_STAMPS
 # Load it with GDSM_LIB=gallocy_amd/<dir>/libgdsm.so (scripts/dev/ab_many.sh).
 set -eu
 cd "$(dirname "$0")/../.."

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of libgdsm builds on the config-4 fold (uniform and Zipf), alternating, same box:
 # coh_fold_kernel ms per launch from bench.py's HIP events. Usage:
-#   scripts/dev/coh_lib_ab.sh OUTDIR ROUNDS lib_dir [lib_dir ...]   (e.g. gallocy_amd/lib gallocy_amd/lib_w1)
+#   scripts/dev/coh_lib_ab.sh OUTDIR ROUNDS lib_dir [lib_dir ...]   (e.g. gallocy_amd/lib gallocy_amd/lib_ab)
 set -u
 OUT=gpurun_out/$1; R=$2; shift 2; mkdir -p $OUT
 for r in $(seq 1 $R); do

@@ -1,8 +1,6 @@
-"""In-process A/B of the twin kernel geometries on the north-star pages: one allocation, variants
-alternating, median kernel time per variant. The round-4 measurement ran with a
-gdsm_tune("twin_variant") knob (0 one page per wave step, 1 two pages + nontemporal loads, 2 two
-pages + nontemporal loads and stores, 3 one page, both nontemporal, 4 four pages); the knob was
-removed with the result, so this now times the kept kernel only."""
+"""In-process timing of the twin kernel on the north-star pages: one allocation, median kernel
+time over the rounds. Round 4 compared five geometries this way; the losing kernels
+and their knob were removed with the result, so this times the kept kernel only."""
 import sys
 from pathlib import Path
 

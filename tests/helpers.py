@@ -1,7 +1,10 @@
 """Shared test helpers: independent pure-numpy restatements used to cross-check the C oracle."""
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
+import pytest
 
 
 def np_runs(twin_page: np.ndarray, cur_page: np.ndarray):
@@ -160,3 +163,32 @@ def py_coherence(state, faults, events, n_pages):
 
 
 from gallocy_amd.workloads import zipf_counts  # noqa: E402,F401
+
+
+# gdsm_tune's keys and their defaults (include/gdsm.h).
+TUNE_DEFAULTS = {"diff_variant": 0, "apply_variant": 0, "diff_solo_max": 0, "diff_chain": 2,
+                 "coh_variant": 0, "coh_chain": 1, "coh_span": 4,
+                 "rounds_xcd": -1, "rounds_lds": -1, "rounds_lds_wg": 0}
+
+
+@contextlib.contextmanager
+def tuned(**keys):
+    """gdsm_tune(key, value) for every given key (each call must return 0); the keys go back to
+    their defaults on the way out, whatever happened inside: the knobs are process-wide."""
+    from gallocy_amd import _lib
+    L = _lib.load()
+    try:
+        for k, v in keys.items():
+            assert L.gdsm_tune(k.encode(), v) == 0, (k, v)
+        yield
+    finally:
+        for k in keys:
+            L.gdsm_tune(k.encode(), TUNE_DEFAULTS[k])
+
+
+@pytest.fixture
+def tune():
+    """tune(key=value, ...) inside a test: tuned() held until the test ends (import the fixture
+    into the test module)."""
+    with contextlib.ExitStack() as stack:
+        yield lambda **keys: stack.enter_context(tuned(**keys))

@@ -168,6 +168,22 @@ def test_tune_rejects_measurement_only_variants():
     for key, ok, default in ((b"diff_solo_max", 16, 0), (b"diff_chain", 3, 2), (b"coh_chain", 0, 1),
                              (b"coh_span", 2, 4)):
         assert L.gdsm_tune(key, ok) == 0 and L.gdsm_tune(key, default) == 0
+    # gdsm_rounds' launch forms: -1 (automatic) / 0 / 1, and the LDS form's workgroup count
+    # (0 = automatic, up to kRoundsLdsMaxWGs = 16)
+    max_wgs = 16
+    try:
+        for key in (b"rounds_xcd", b"rounds_lds"):
+            for bad in (-2, 2):
+                assert L.gdsm_tune(key, bad) == -22, (key, bad)
+            for ok in (-1, 0, 1):
+                assert L.gdsm_tune(key, ok) == 0, (key, ok)
+        for bad in (-1, max_wgs + 1):
+            assert L.gdsm_tune(b"rounds_lds_wg", bad) == -22, bad
+        for ok in (0, 3, max_wgs):
+            assert L.gdsm_tune(b"rounds_lds_wg", ok) == 0, ok
+    finally:
+        for key, default in ((b"rounds_xcd", -1), (b"rounds_lds", -1), (b"rounds_lds_wg", 0)):
+            assert L.gdsm_tune(key, default) == 0
 
 
 @pytest.mark.skipif(bool(__import__("os").environ.get("GDSM_LIB")),

@@ -6,6 +6,7 @@ import pytest
 
 from gallocy_amd.replay import MmultReplay
 from oracle import oracle
+from tests.helpers import tune  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,19 +32,19 @@ def test_mmult_replay_end_to_end(ndim, nodes, graph, fused):
     (1000, 2, True, "device"), (1000, 4, True, "device"), (1000, 8, True, "device"),
     (1000, 1, True, "device-grid"), (1000, 4, True, "device-grid"),
     (1000, 1, True, "device-gridfold"), (1000, 8, True, "device-gridfold")])
-def test_mmult_replay_other_drivers(ndim, nodes, retwin, driver, monkeypatch):
+def test_mmult_replay_other_drivers(ndim, nodes, retwin, driver, tune):
     """The same replay with every round issued from Python (MmultReplay.round, driver="python"),
     by two C++ threads, one per context (driver="native2"), or on the device (driver="device":
     gdsm_rounds, one persistent launch per context with device-wide barriers between a round's
     steps), with and without the re-twinning release: the same home copies, totals and page
-    table. "device-grid": gdsm_rounds on the whole grid (GDSM_ROUNDS_XCD=0) instead of the
+    table. "device-grid": gdsm_rounds on the whole grid (gdsm_tune "rounds_xcd" 0) instead of the
     one-XCD team it takes for rounds this small; "device-gridfold": the page-table rounds on the
-    persistent grid (GDSM_ROUNDS_LDS=0) instead of one workgroup with the table in LDS."""
+    persistent grid (gdsm_tune "rounds_lds" 0) instead of one workgroup with the table in LDS."""
     if driver == "device-grid":
-        monkeypatch.setenv("GDSM_ROUNDS_XCD", "0")
+        tune(rounds_xcd=0)
         driver = "device"
     if driver == "device-gridfold":
-        monkeypatch.setenv("GDSM_ROUNDS_LDS", "0")
+        tune(rounds_lds=0)
         driver = "device"
     _check_replay(MmultReplay(ndim=ndim, nodes=nodes, seed=7, retwin=retwin, driver=driver),
                   nodes, False)
@@ -51,14 +52,14 @@ def test_mmult_replay_other_drivers(ndim, nodes, retwin, driver, monkeypatch):
 
 @pytest.mark.parametrize("xcd", ["0", "1"])
 @pytest.mark.parametrize("ndim,nodes", [(1000, 1), (257, 3), (1000, 8)])
-def test_device_rounds_stream_equals_the_issued_rounds(ndim, nodes, xcd, monkeypatch):
+def test_device_rounds_stream_equals_the_issued_rounds(ndim, nodes, xcd, tune):
     """gdsm_rounds (every round in one persistent launch per context) leaves the same last-round
     stream, the same TWIN and CURRENT views and the same home copy as the C++-issued rounds (one
     chained release launch per round): the stream checks the record bytes and offsets that no
     home-copy comparison sees. Both forms of the launch: the whole grid with write-through
-    hand-offs (GDSM_ROUNDS_XCD=0) and the one-XCD team whose hand-offs meet in its L2 (=1, the
-    default at these round sizes)."""
-    monkeypatch.setenv("GDSM_ROUNDS_XCD", xcd)
+    hand-offs (gdsm_tune "rounds_xcd" 0) and the one-XCD team whose hand-offs meet in its L2 (1,
+    the default at these round sizes)."""
+    tune(rounds_xcd=int(xcd))
     Rs = [MmultReplay(ndim=ndim, nodes=nodes, seed=11, driver=d) for d in ("native", "device")]
     try:
         out = []

@@ -8,10 +8,10 @@ state is carried across calls. tests/test_rounds_model.py checks the model and t
 CPU.
 
 Launch forms: a call whose largest round has <= 32 pages runs on a one-XCD team by default, a
-larger one on the whole grid; GDSM_ROUNDS_XCD=0 / 1 forces the form. The edges, hand-off,
-sizes-small and mmult traces run with the variable unset (the team), "0" and "1"; sizes-large with
-it unset (the whole grid: its 33- to 2048-page rounds are past the team's domain; rounds of more
-than 256 pages make a workgroup release several pages per round)."""
+larger one on the whole grid; gdsm_tune "rounds_xcd" 0 / 1 forces the form. The edges, hand-off,
+sizes-small and mmult traces run with the key at -1 (automatic: the team), 0 and 1; sizes-large
+with it at -1 (the whole grid: its 33- to 2048-page rounds are past the team's domain; rounds of
+more than 256 pages make a workgroup release several pages per round)."""
 import errno
 import functools
 
@@ -22,7 +22,7 @@ import gallocy_amd as ga
 from gallocy_amd.gdsm import check, lib
 from oracle import oracle
 from tests import rounds_model as rm
-from tests.helpers import zipf_counts
+from tests.helpers import tune, zipf_counts  # noqa: F401  (tune: fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -30,11 +30,9 @@ XCD = [None, "0", "1"]
 ARENAS = ("twin", "current", "replica")
 
 
-def _set_xcd(monkeypatch, xcd):
-    if xcd is None:
-        monkeypatch.delenv("GDSM_ROUNDS_XCD", raising=False)
-    else:
-        monkeypatch.setenv("GDSM_ROUNDS_XCD", xcd)
+def _set_xcd(tune, xcd):
+    """gdsm_tune "rounds_xcd": None = -1 (automatic), "0" = the whole grid, "1" = the team."""
+    tune(rounds_xcd=-1 if xcd is None else int(xcd))
 
 
 @functools.lru_cache(maxsize=None)
@@ -68,14 +66,14 @@ def _assert_equal(got, want, what):
 
 @pytest.mark.parametrize("xcd", XCD)
 @pytest.mark.parametrize("name", ["edges", "hand-off", "sizes-small"])
-def test_rounds_data_matches_model_at_every_prefix(name, xcd, monkeypatch):
+def test_rounds_data_matches_model_at_every_prefix(name, xcd, tune):
     """edges: every prefix of the 8 edge-case rounds (rounds_model.edges_trace: clean and
     pre-dirtied entries, half-chunk and zero-byte descriptors, runs across the waves' quarter
     edges, a descriptor over three pages, a full and a maximum-size record, two views to one home
     page, empty first / middle / last rounds). hand-off: 1, 2, 17 and 300 rounds on the same three
     pages, the list rotated every round. sizes-small: every prefix of rounds of 1, 32, 0, 17, 31
     and 2 pages."""
-    _set_xcd(monkeypatch, xcd)
+    _set_xcd(tune, xcd)
     t, wants = _trace(name), _wants(name)
     for k in PREFIXES[name]:
         got = rm.run_prefix(t, k)
@@ -86,12 +84,12 @@ def test_rounds_data_matches_model_at_every_prefix(name, xcd, monkeypatch):
             assert int(np.diff(got.rec_off)[1]) == ga.gdsm.MAX_RECORD == 10244
 
 
-def test_rounds_data_large_rounds_match_model_at_every_prefix(monkeypatch):
+def test_rounds_data_large_rounds_match_model_at_every_prefix(tune):
     """sizes-large: rounds of 1, 33, 0, 257, 32, 2048, 5 and 256 pages on a 4096-page arena, every
     prefix: the whole grid chosen automatically (> 32 pages), one workgroup releasing several
     pages of a round and looking back across its own iterations (> 256 pages), the 2048-page
     limit."""
-    _set_xcd(monkeypatch, None)
+    _set_xcd(tune, None)
     t = _trace("sizes-large")
     for k, want in enumerate(rm.replay(t), 1):
         _assert_equal(rm.run_prefix(t, k), want, ("sizes-large", k))
@@ -118,12 +116,12 @@ def _mmult_trace(R):
 
 @pytest.mark.parametrize("xcd", XCD)
 @pytest.mark.parametrize("ndim,nodes", [(64, 1), (257, 3), (64, 8)])
-def test_mmult_device_rounds_match_model(ndim, nodes, xcd, monkeypatch):
+def test_mmult_device_rounds_match_model(ndim, nodes, xcd, tune):
     """Config 5's trace (MmultReplay, driver="device") as a model trace: after run(), the last
     round's stream, TWIN, CURRENT and the home copy equal the model's (the oracle's diff of every
     round), not only those of another HIP path."""
     from gallocy_amd.replay import MmultReplay
-    _set_xcd(monkeypatch, xcd)
+    _set_xcd(tune, xcd)
     R = MmultReplay(ndim=ndim, nodes=nodes, seed=11, driver="device")
     try:
         t = _mmult_trace(R)

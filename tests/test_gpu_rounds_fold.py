@@ -1,10 +1,10 @@
 """gdsm_rounds' page-table side on its own (docs/SPEC.md §5, rounds folded in order): random
 multi-round batches against the C oracle's sequential fold, round by round (page-table words,
 per-page faults, every round's totals row). Both forms of the launch: workgroups that keep
-slices of the page table in LDS (GDSM_ROUNDS_LDS=1, the default wherever it fits: up to 16 slices
-of <= 8192 pages, rounds of <= 16384 events, <= 2048 rounds) and the persistent grid
-(GDSM_ROUNDS_LDS=0, the form larger tables and rounds take). The data
-side gets empty rounds (no pages), so only the fold runs."""
+slices of the page table in LDS (gdsm_tune "rounds_lds" 1, the default wherever it fits: up to
+16 slices of <= 8192 pages, rounds of <= 16384 events, <= 2048 rounds) and the persistent grid
+(gdsm_tune "rounds_lds" 0, the form larger tables and rounds take). The data side gets empty
+rounds (no pages), so only the fold runs."""
 import ctypes as C
 
 import numpy as np
@@ -13,7 +13,7 @@ import pytest
 import gallocy_amd as ga
 from gallocy_amd.gdsm import GdsmError, check, lib
 from oracle import oracle
-from tests.helpers import zipf_counts
+from tests.helpers import tune, zipf_counts  # noqa: F401  (tune: fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -72,12 +72,12 @@ def _oracle_rounds(n_pages, n_nodes, rounds, st0=None, fl0=None):
     (LDS_PAGES, 5, [LDS_EVENTS, 3, LDS_EVENTS]),   # both LDS limits at once
     (100, 2, [900, 1200, 64, 7]),                 # long page runs across thread chunks
 ])
-def test_rounds_fold_matches_oracle(n_pages, n_nodes, sizes, lds, monkeypatch):
-    """lds "1-wg3": the LDS form on three workgroups (GDSM_ROUNDS_LDS_WG=3), each folding the
+def test_rounds_fold_matches_oracle(n_pages, n_nodes, sizes, lds, tune):
+    """lds "1-wg3": the LDS form on three workgroups (gdsm_tune "rounds_lds_wg" 3), each folding the
     events of its third of the table."""
-    monkeypatch.setenv("GDSM_ROUNDS_LDS", lds[0])
+    tune(rounds_lds=int(lds[0]))
     if lds.endswith("wg3"):
-        monkeypatch.setenv("GDSM_ROUNDS_LDS_WG", "3")
+        tune(rounds_lds_wg=3)
     rounds = [_round_events(n_pages, n, n_nodes, seed=40 + i, write_pct=(10, 35, 70)[i % 3])
               for i, n in enumerate(sizes)]
     got = _run_rounds(n_pages, n_nodes, rounds)
@@ -87,10 +87,10 @@ def test_rounds_fold_matches_oracle(n_pages, n_nodes, sizes, lds, monkeypatch):
 
 
 @pytest.mark.parametrize("lds", ["1", "0"])
-def test_rounds_fold_arbitrary_table_states(lds, monkeypatch):
+def test_rounds_fold_arbitrary_table_states(lds, tune):
     """Uploaded words in any state (INVALID, the unused state 3, owners >= 8, dirty, fault counts
     near 2^32, which wrap)."""
-    monkeypatch.setenv("GDSM_ROUNDS_LDS", lds)
+    tune(rounds_lds=int(lds))
     n = 3000
     rng = np.random.default_rng(5)
     st0 = rng.integers(0, 1 << 19, n).astype(np.uint32)
@@ -104,7 +104,7 @@ def test_rounds_fold_arbitrary_table_states(lds, monkeypatch):
 
 def test_rounds_fold_past_the_lds_limits_takes_the_grid():
     """A round of more than 16384 events (or a table of more than 8192 pages) folds on the
-    persistent grid by default, and GDSM_ROUNDS_LDS=1 refuses it."""
+    persistent grid by default, and gdsm_tune "rounds_lds" 1 refuses it."""
     n = LDS_PAGES + 1
     rounds = [_round_events(n, LDS_EVENTS + 1, 8, seed=90, write_pct=25)]
     got = _run_rounds(n, 8, rounds)
@@ -113,8 +113,8 @@ def test_rounds_fold_past_the_lds_limits_takes_the_grid():
         assert np.array_equal(g, w)
 
 
-def test_rounds_fold_lds_forced_past_its_limits_is_refused(monkeypatch):
-    monkeypatch.setenv("GDSM_ROUNDS_LDS", "1")
+def test_rounds_fold_lds_forced_past_its_limits_is_refused(tune):
+    tune(rounds_lds=1)
     with pytest.raises(GdsmError) as ei:
         _run_rounds(16, 8, [_round_events(16, LDS_EVENTS + 1, 8, seed=3, write_pct=25)])
     assert ei.value.errno == 22
@@ -122,10 +122,10 @@ def test_rounds_fold_lds_forced_past_its_limits_is_refused(monkeypatch):
 
 @pytest.mark.parametrize("lds", ["1", "0"])
 @pytest.mark.parametrize("bad", ["unsorted", "page", "node", "high"])
-def test_rounds_fold_rejects_bad_events(bad, lds, monkeypatch):
+def test_rounds_fold_rejects_bad_events(bad, lds, tune):
     """An unsorted round, a page outside the table, a node >= n_nodes or a set high dword fails
     the call (EINVAL at the sync), as gdsm_coherence_batch does."""
-    monkeypatch.setenv("GDSM_ROUNDS_LDS", lds)
+    tune(rounds_lds=int(lds))
     good = _round_events(500, 3000, 4, seed=11, write_pct=25)
     ev = good.copy()
     if bad == "unsorted":
@@ -142,11 +142,11 @@ def test_rounds_fold_rejects_bad_events(bad, lds, monkeypatch):
 
 
 @pytest.mark.parametrize("lds", ["auto", "1"])
-def test_rounds_fold_more_rounds_than_lds_offsets(lds, monkeypatch):
+def test_rounds_fold_more_rounds_than_lds_offsets(lds, tune):
     """2049 rounds: more event offsets than the LDS form stages (2048), so the default takes the
-    persistent grid and GDSM_ROUNDS_LDS=1 refuses the call; 2048 rounds still fold in LDS."""
+    persistent grid and gdsm_tune "rounds_lds" 1 refuses the call; 2048 rounds still fold in LDS."""
     if lds == "1":
-        monkeypatch.setenv("GDSM_ROUNDS_LDS", "1")
+        tune(rounds_lds=1)
     rounds = [_round_events(64, 3, 4, seed=500 + i, write_pct=40) for i in range(2049)]
     if lds == "1":
         with pytest.raises(GdsmError) as ei:
@@ -160,12 +160,12 @@ def test_rounds_fold_more_rounds_than_lds_offsets(lds, monkeypatch):
 
 
 @pytest.mark.parametrize("wg", ["", "3"])
-def test_rounds_fold_lds_slices_a_larger_table(wg, monkeypatch):
+def test_rounds_fold_lds_slices_a_larger_table(wg, tune):
     """A table of 20000 pages (more than one workgroup's 8192) in the LDS form: three or four
     slices, Zipf rounds whose runs cross the slices' edges, and 8192-page multiples."""
-    monkeypatch.setenv("GDSM_ROUNDS_LDS", "1")
+    tune(rounds_lds=1)
     if wg:
-        monkeypatch.setenv("GDSM_ROUNDS_LDS_WG", wg)
+        tune(rounds_lds_wg=int(wg))
     n = 20000
     rounds = [_round_events(n, m, 8, seed=600 + i, write_pct=30)
               for i, m in enumerate([16000, 9000, 1, 12000])]
@@ -176,11 +176,11 @@ def test_rounds_fold_lds_slices_a_larger_table(wg, monkeypatch):
 
 
 @pytest.mark.parametrize("bad", ["unsorted", "across"])
-def test_rounds_fold_lds_slices_reject_unsorted_rounds(bad, monkeypatch):
+def test_rounds_fold_lds_slices_reject_unsorted_rounds(bad, tune):
     """Unsorted rounds on three slices: a swap inside one slice, and one that moves an event into
     another slice's index range."""
-    monkeypatch.setenv("GDSM_ROUNDS_LDS", "1")
-    monkeypatch.setenv("GDSM_ROUNDS_LDS_WG", "3")
+    tune(rounds_lds=1)
+    tune(rounds_lds_wg=3)
     good = _round_events(600, 6000, 4, seed=21, write_pct=25)
     ev = good.copy()
     if bad == "unsorted":
