@@ -133,6 +133,12 @@ SIGNATURES = {
     "gdsm_dirty_scan_workspace_bytes": (C.c_uint64, [C.c_uint64]),
     "gdsm_dirty_scan_raw": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp,
                                       C.c_uint64, vp]),
+    "gdsm_runs_split": (C.c_int, [vp, C.POINTER(GdsmRuns), vp, vp, C.c_uint64, C.c_uint32,
+                                  C.POINTER(GdsmRuns), C.POINTER(vp), u64p, C.c_uint32]),
+    "gdsm_runs_split_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "gdsm_runs_split_raw": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_uint64,
+                                      C.c_uint32, C.POINTER(vp), C.POINTER(vp), u64p, u64p,
+                                      C.POINTER(vp), vp, vp, C.c_uint32, vp, C.c_uint64, vp]),
     "gdsm_exchange": (C.c_int, [vp, vp, C.POINTER(GdsmRuns), C.POINTER(vp), C.POINTER(GdsmRuns),
                                 C.POINTER(vp), C.c_int, C.c_uint32]),
 }

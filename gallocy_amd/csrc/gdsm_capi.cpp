@@ -272,6 +272,7 @@ int gdsm_fini(gdsm_ctx* ctx) {
   if (ctx->merge_ws) (void)hipFree(ctx->merge_ws);
   if (ctx->fetch_ws) (void)hipFree(ctx->fetch_ws);
   if (ctx->dirty_ws) (void)hipFree(ctx->dirty_ws);
+  if (ctx->split_ws) (void)hipFree(ctx->split_ws);
   for (auto* p : ctx->ids_safe)
     if (p) (void)hipFree(p);
   for (auto& kv : ctx->runs_busy) (void)hipEventDestroy(kv.second);
@@ -939,6 +940,109 @@ int gdsm_dirty_scan_raw(const uint8_t* a, const uint8_t* b, const uint32_t* ids,
   GDSM_TRY(gdsm::launch_dirty_scan(a, b, ids, n, ~0ull, pages_out, pos_out, cap, stats, nullptr,
                                    static_cast<uint8_t*>(workspace), workspace_bytes,
                                    static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+// ---- stream split (SPEC §13) -------------------------------------------------------------
+uint64_t gdsm_runs_split_workspace_bytes(uint64_t n, uint32_t G) {
+  return gdsm::split_workspace_bytes(n, G);
+}
+
+// The argument rules both forms share, checked before anything is enqueued (and before a context
+// is touched); fills the launcher's view.
+static int split_args(const uint64_t* rec_off, const uint8_t* data, uint64_t cap,
+                      const uint32_t* ids, const uint32_t* dest, uint64_t per, uint64_t n,
+                      uint32_t G, uint64_t* const* out_rec_off, uint8_t* const* out_data,
+                      const uint64_t* out_caps, const uint64_t* out_n_caps,
+                      uint32_t* const* out_ids, uint32_t flags, gdsm::SplitArgs* a) {
+  if (G == 0 || G > GDSM_MAX_NODES || !rec_off || (!data && cap)) return -EINVAL;
+  if ((dest != nullptr) == (per != 0)) return -EINVAL;  // exactly one of the two forms
+  if (reinterpret_cast<uintptr_t>(data) & 3) return -EINVAL;  // records are moved in dwords
+  if (flags & ~GDSM_SPLIT_DROP_EMPTY) return -EINVAL;
+  if (n > (1ull << 32)) return -EINVAL;
+  if (!out_rec_off || !out_data || !out_caps || !out_n_caps) return -EINVAL;
+  *a = gdsm::SplitArgs{};
+  a->rec_off = rec_off;
+  a->data = data;
+  a->cap = cap;
+  a->ids = ids;
+  a->dest = dest;
+  a->per = per;
+  a->n = n;
+  a->G = G;
+  a->flags = flags;
+  for (uint32_t d = 0; d < G; ++d) {
+    if (!out_rec_off[d] || (!out_data[d] && out_caps[d])) return -EINVAL;
+    if (reinterpret_cast<uintptr_t>(out_data[d]) & 3) return -EINVAL;
+    if (out_rec_off[d] == rec_off || (out_data[d] && out_data[d] == data)) return -EINVAL;
+    for (uint32_t e = 0; e < d; ++e)
+      if (out_rec_off[d] == out_rec_off[e] || (out_data[d] && out_data[d] == out_data[e]))
+        return -EINVAL;
+    a->out_rec_off[d] = out_rec_off[d];
+    a->out_data[d] = out_data[d];
+    a->out_cap[d] = out_caps[d];
+    a->out_n_cap[d] = out_n_caps[d];
+    a->out_ids[d] = out_ids ? out_ids[d] : nullptr;
+  }
+  return 0;
+}
+
+int gdsm_runs_split(gdsm_ctx* ctx, const gdsm_runs* in, const uint32_t* ids, const uint32_t* dest,
+                    uint64_t per, uint32_t G, gdsm_runs* out, uint32_t* const* out_ids,
+                    uint64_t* counts, uint32_t flags) {
+  if (!ctx || !in || !out || G == 0 || G > GDSM_MAX_NODES) return -EINVAL;
+  uint64_t* ro[GDSM_MAX_NODES];
+  uint8_t* data[GDSM_MAX_NODES];
+  uint64_t caps[GDSM_MAX_NODES], ncaps[GDSM_MAX_NODES];
+  for (uint32_t d = 0; d < G; ++d) {
+    ro[d] = out[d].rec_off;
+    data[d] = out[d].data;
+    caps[d] = out[d].cap;
+    ncaps[d] = out[d].n_cap;
+  }
+  gdsm::SplitArgs a;
+  int rc = split_args(in->rec_off, in->data, in->cap, ids, dest, per, in->n, G, ro, data, caps,
+                      ncaps, out_ids, flags, &a);
+  if (rc) return rc;
+  if (recording(ctx)) return -EBUSY;  // the call reads the counts back
+  CtxGuard g(ctx);
+  if (g.rc) return g.rc;
+  rc = ensure(ctx, &ctx->split_ws, &ctx->split_ws_bytes, gdsm::split_workspace_bytes(a.n, G));
+  if (rc) return rc;
+  for (uint32_t d = 0; d < G; ++d) out[d].n = 0;
+  // header: [0] fatal, [4] this call's own error word (ctx->err keeps what earlier calls left for
+  // gdsm_sync), [64 ..) the 2G counts
+  hipStream_t s = ctx->stream;
+  uint32_t* lerr = reinterpret_cast<uint32_t*>(ctx->split_ws) + 1;
+  uint64_t* cnt = reinterpret_cast<uint64_t*>(ctx->split_ws + 64);
+  GDSM_TRY(hipMemsetAsync(lerr, 0, 4, s));
+  GDSM_TRY(gdsm::launch_runs_split(a, cnt, lerr, ctx->split_ws, ctx->split_ws_bytes, s));
+  uint64_t h[8 + 2 * GDSM_MAX_NODES];  // the header's first 64 bytes, then the counts
+  GDSM_TRY(hipMemcpyAsync(h, ctx->split_ws, 64 + 16 * (size_t)G, hipMemcpyDeviceToHost, s));
+  GDSM_TRY(hipStreamSynchronize(s));
+  if (counts) memcpy(counts, h + 8, 16 * (size_t)G);
+  if (h[0]) return -EINVAL;  // the fatal word or this call's error bits
+  for (uint32_t d = 0; d < G; ++d)
+    if (h[8 + 2 * d] > out[d].n_cap || h[9 + 2 * d] > out[d].cap) return -ENOSPC;
+  for (uint32_t d = 0; d < G; ++d) out[d].n = h[8 + 2 * d];
+  return 0;
+}
+
+int gdsm_runs_split_raw(const uint64_t* rec_off, const uint8_t* data, uint64_t cap,
+                        const uint32_t* ids, const uint32_t* dest, uint64_t per, uint64_t n,
+                        uint32_t G, uint64_t* const* out_rec_off, uint8_t* const* out_data,
+                        const uint64_t* out_caps, const uint64_t* out_n_caps,
+                        uint32_t* const* out_ids, uint64_t* counts, uint32_t* err, uint32_t flags,
+                        void* workspace, uint64_t workspace_bytes, void* stream) {
+  gdsm::SplitArgs a;
+  int rc = split_args(rec_off, data, cap, ids, dest, per, n, G, out_rec_off, out_data, out_caps,
+                      out_n_caps, out_ids, flags, &a);
+  if (rc) return rc;
+  if (!counts || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 7) ||
+      workspace_bytes < gdsm::split_workspace_bytes(n, G))
+    return -EINVAL;
+  GDSM_TRY(gdsm::launch_runs_split(a, counts, err, static_cast<uint8_t*>(workspace),
+                                   workspace_bytes, static_cast<hipStream_t>(stream)));
   return 0;
 }
 

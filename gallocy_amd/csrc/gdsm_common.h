@@ -106,6 +106,18 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
   return (uint64_t)lo | ((uint64_t)hi << 32);
 }
 
+// Inclusive prefix sum of a u64 across the 64 lanes (lane shuffles: a DPP step moves 32 bits, and
+// the two halves of a sum cannot be added apart).
+__device__ __forceinline__ uint64_t wave_incl_sum64(uint64_t x) {
+  const uint32_t lane = lane_id();
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint64_t y = shfl64(x, (int)lane - d);
+    if (lane >= (uint32_t)d) x += y;
+  }
+  return x;
+}
+
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return lane_bcast(wave_incl_sum(v), 63); }
 
 // Value of lane l-1 (lane 0 gets 0) / of lane l+1 (lane 63 gets 0).

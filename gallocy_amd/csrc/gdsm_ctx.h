@@ -68,6 +68,9 @@ struct gdsm_ctx {
   // gdsm_dirty_scan: tile offsets, flag words and bounds
   uint8_t* dirty_ws = nullptr;
   uint64_t dirty_ws_bytes = 0;
+  // gdsm_runs_split: the fatal word, the call's own error word, the counts and the tile sums
+  uint8_t* split_ws = nullptr;
+  uint64_t split_ws_bytes = 0;
   // checked copies of caller page-id lists (launch_check_ids): one per stream, so an async
   // apply's list is never overwritten by a call on the main stream
   // [2]: the target-page list of gdsm_diff_apply_ids (main stream, beside [0])

@@ -297,6 +297,38 @@ hipError_t launch_dirty_scan(const uint8_t* a, const uint8_t* b, const uint32_t*
                              uint64_t cap, uint64_t* stats, uint32_t* err, uint8_t* ws,
                              uint64_t ws_bytes, hipStream_t s);
 
+// Stream split (SPEC §13; gdsm_split.hip): the stream rec_off[n+1] / data[cap] partitioned stably
+// into G streams. dest (n masks, bit d = stream d) or, with dest NULL, the home ids[i] / per with
+// the page rewritten to ids[i] - home x per (ids NULL: page i); flags: GDSM_SPLIT_DROP_EMPTY. Every
+// write is guarded: out_rec_off[d][j] for j <= out_n_cap[d], out_ids[d][j] (an entry may be NULL)
+// for j < out_n_cap[d], data below out_cap[d] in whole dwords.
+constexpr uint32_t kSplitTile = 256;     // records per tile of the counts and their scan
+constexpr uint64_t kSplitHeader = 256;   // workspace bytes before the tile sums; [0, 4) the fatal word
+struct SplitArgs {
+  const uint64_t* rec_off;
+  const uint8_t* data;
+  uint64_t cap;
+  const uint32_t* ids;
+  const uint32_t* dest;
+  uint64_t per;
+  uint64_t n;
+  uint32_t G;
+  uint32_t flags;
+  uint64_t* out_rec_off[8];
+  uint8_t* out_data[8];
+  uint64_t out_cap[8];
+  uint64_t out_n_cap[8];
+  uint32_t* out_ids[8];
+};
+uint64_t split_workspace_bytes(uint64_t n, uint32_t G);
+// counts (device, 2G u64): {records, bytes} per stream, the true values whatever the capacities;
+// err |= 16 for malformed input offsets, 8 for a destination >= G (err may be NULL): the outputs are
+// then empty (counts 0, rec_off[0] = 0, no data written). ws: 8-byte aligned,
+// split_workspace_bytes(n, G); the launcher uses its first 4 bytes and the tile sums, the rest of
+// the header is the caller's. Five launches and a memset on s, no host synchronisation.
+hipError_t launch_runs_split(const SplitArgs& a, uint64_t* counts, uint32_t* err, uint8_t* ws,
+                             uint64_t ws_bytes, hipStream_t s);
+
 // GPU NW alignment (legacy diff()): workspace per pair and the fill + trace launches.
 uint64_t nw_pair_ws_bytes(uint32_t max_len);
 hipError_t launch_nw(const uint8_t* a, const uint64_t* a_off, const uint8_t* b,

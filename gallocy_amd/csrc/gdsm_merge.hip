@@ -272,12 +272,7 @@ __global__ __launch_bounds__(64) void merge_scan_top_kernel(uint64_t* __restrict
   uint64_t carry = 0;
   for (uint64_t b = 0; b < nt; b += 64) {
     const uint64_t x = b + lane < nt ? tsum[b + lane] : 0;
-    uint64_t inc = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t y = shfl64(inc, (int)lane - d);
-      if (lane >= (uint32_t)d) inc += y;
-    }
+    const uint64_t inc = wave_incl_sum64(x);
     if (b + lane < nt) tsum[b + lane] = carry + inc - x;
     carry += shfl64(inc, 63);
   }

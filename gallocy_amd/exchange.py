@@ -230,6 +230,15 @@ def exchange_runs(ctx: gdsm.Context, comm: Comm, send: list, send_ids: list, rec
         recv[s].s.n = r_arr[s].n
 
 
+def split_by_home(ctx: gdsm.Context, runs: gdsm.Runs, pages, total_pages: int, world: int,
+                  outs=None) -> "gdsm.SplitResult":
+    """A sparse release's stream (the diff of a dirty list; `pages` its GLOBAL page ids on the
+    device, e.g. DirtyList.pages) as exchange_runs' arguments: res.runs is `send`, [b.ptr for b in
+    res.ids] is `send_ids`. gdsm_runs_split's home form with per = ceil(total_pages / world)."""
+    per = -(-int(total_pages) // int(world))
+    return ctx.runs_split(runs, ids=pages, per=per, G=world, outs=outs)
+
+
 def exchange_gloo(ctx: gdsm.Context, gloo: GlooTransport, send: list, send_ids: list,
                   counts: list, rank: int):
     """The same release over GlooTransport with host staging (one-GPU multi-rank rehearsal):

@@ -21,6 +21,8 @@ MAX_RECORD = 10244
 TWIN, CURRENT, REPLICA = 0, 1, 2
 GEN_UNIFORM, GEN_CLUSTERED = 0, 1
 RELEASE_RETWIN = 1  # gdsm.h GDSM_RELEASE_RETWIN
+SPLIT_DROP_EMPTY = 1  # gdsm.h GDSM_SPLIT_DROP_EMPTY
+MAX_NODES = 8
 _ARENA = {"twin": TWIN, "current": CURRENT, "replica": REPLICA,
           TWIN: TWIN, CURRENT: CURRENT, REPLICA: REPLICA}
 
@@ -205,6 +207,25 @@ class DirtyList:
         for b in (self.pages, self.pos, self._stats):
             if b is not None and b.ptr:
                 b.free()
+
+
+class SplitResult:
+    """What Context.runs_split returns: `runs` (the G output streams, `n` set), `ids` (per stream the
+    DeviceBuffer of its records' pages) and `counts` (uint64[G, 2]: records and bytes per
+    destination, also when the call ended with -ENOSPC)."""
+
+    def __init__(self, ctx, runs, ids, counts, own):
+        self.ctx, self.runs, self.ids, self.counts = ctx, runs, ids, counts
+        self._own = own
+
+    def free(self):
+        """Frees the streams and page lists runs_split() allocated (not those passed as outs)."""
+        for b in self._own:
+            if isinstance(b, Runs):
+                b.free()
+            elif b is not None and b.ptr:
+                b.free()
+        self._own = []
 
 
 class Graph:
@@ -456,6 +477,46 @@ class Context:
                                     self._ptr(pages), self._ptr(pos), cap, stats.ptr),
               "gdsm_dirty_scan")
         return DirtyList(self, pages, pos, stats, cap)
+
+    def runs_split(self, runs: Runs, ids=None, dest=None, per: int = 0, G: int = 0,
+                   drop_empty: bool = False, outs=None) -> "SplitResult":
+        """gdsm_runs_split (docs/SPEC.md §13): the stream `runs` (pages `ids`, a DeviceBuffer or
+        device pointer; None = page i) partitioned stably into G streams: by `dest` (device masks,
+        bit d = stream d) or, with per > 0, by home ids[i] // per with the page rewritten to the
+        home's index. outs: G pairs (Runs, DeviceBuffer or None) to write into; None allocates every
+        output for the worst case (all of the input's records and bytes). Synchronises; on -ENOSPC
+        the GdsmError carries the counts needed as its `counts` attribute."""
+        G = int(G)
+        if not 1 <= G <= MAX_NODES:
+            raise ValueError("G must be 1 .. 8")
+        own = []
+        if outs is None:
+            outs = []
+            for _ in range(G):
+                r = Runs(self, max(runs.n, 1), max(runs.cap, 16))
+                b = self.buffer(4 * max(runs.n, 1))
+                own += [r, b]
+                outs.append((r, b))
+        if len(outs) != G:
+            raise ValueError("one (Runs, ids buffer) pair per destination")
+        arr = (GdsmRuns * G)(*[o[0].s for o in outs])
+        idp = (C.c_void_p * G)(*[self._ptr(o[1]) for o in outs])
+        counts = np.zeros((G, 2), np.uint64)
+        rc = lib().gdsm_runs_split(self.handle, C.byref(runs.s), self._ptr(ids), self._ptr(dest),
+                                   int(per), G, arr, idp,
+                                   counts.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                   SPLIT_DROP_EMPTY if drop_empty else 0)
+        for d in range(G):
+            outs[d][0].s.n = arr[d].n
+        res = SplitResult(self, [o[0] for o in outs], [o[1] for o in outs], counts, own)
+        if rc < 0:
+            res.free()
+            try:
+                check(rc, "gdsm_runs_split")
+            except GdsmError as e:
+                e.counts = counts
+                raise
+        return res
 
     def _count(self, ids, n):
         if n is not None:

@@ -660,6 +660,63 @@ int gdsm_dirty_scan_raw(const uint8_t* a, const uint8_t* b, const uint32_t* ids,
                         uint32_t* pages_out, uint32_t* pos_out, uint64_t cap, uint64_t* stats,
                         void* workspace, uint64_t workspace_bytes, void* stream);
 
+/* ---- stream split: one diff stream into one per destination (docs/SPEC.md §13) ---------------
+ * The joint between a stream and the calls that want one stream per destination: gdsm_exchange's
+ * send[] (a sparse release: gdsm_dirty_scan -> gdsm_diff of the list -> split by home -> exchange)
+ * and a home forwarding a merged stream to the nodes that hold copies of its pages. A stable
+ * multi-way partition of the n = in->n records of `in`; records are opaque here (copied byte for
+ * byte, not validated: the apply at the destination does that as usual).
+ *   ids      device, n u32: the page of record i; NULL = page i;
+ *   out      HOST array of G streams, 1 <= G <= GDSM_MAX_NODES, each with its own buffers;
+ *   out_ids  HOST array of G device arrays, out_ids[d] of at least out[d].n_cap entries: the pages
+ *            of out[d]'s records. The array or single entries may be NULL (not written).
+ * Mask form (dest != NULL, per == 0): dest is a device array of n u32; record i goes to every
+ * out[d] with bit d of dest[i] set (0: nowhere; several bits: several copies); the page written is
+ * ids[i]. Home form (dest == NULL, per > 0): record i goes to d = ids[i] / per only and the page
+ * written is ids[i] - d * per, the REPLICA index at home d of SPEC §5b / §9, so out[] and out_ids[]
+ * are gdsm_exchange's send[] and send_ids[] as they stand. With GDSM_SPLIT_DROP_EMPTY a 0-byte
+ * record goes nowhere in either form.
+ * Result: record j of out[d] is the j-th selected record in input order, equal to it byte for byte;
+ * rec_off[0 .. c_d] of out[d] is written from 0; ascending input ids give ascending ids in every
+ * output (an output can be one of gdsm_merge's inputs); in the home form with ascending ids and no
+ * flag the outputs' data concatenated in d order is the input's data.
+ * Runs on the context stream after what was enqueued, synchronises once at the end (one host read
+ * of the counts, as gdsm_notices_fetch_list) and sets out[d].n = c_d. counts: HOST array of 2G u64,
+ * {records, bytes} per destination, may be NULL.
+ *   -ENOSPC  some c_d > out[d].n_cap or b_d > out[d].cap: counts holds what is needed, every
+ *            out[d].n is 0, no buffer was written at or past its capacity;
+ *   -EINVAL  the input offsets do not start at 0, decrease, are not 4-aligned or end past in->cap
+ *            (checked before any record is read, as the merge does), a mask has a bit >= G, or a
+ *            page's home is >= G: nothing is written to any output's data, every out[d].n is 0 and
+ *            the counts are 0. Only this call's own checks decide its return: an error bit an
+ *            earlier unsynchronised call left stays for gdsm_sync (as gdsm_coherence_notify);
+ *   -EBUSY   on a recording context.
+ * Immediate -EINVAL: NULL ctx, in or out; G of 0 or more than 8; both or neither of dest and per;
+ * unknown flags; n > 2^32; an output sharing data or rec_off with the input or with another output;
+ * a data pointer (the input's or an output's) that is not 4-byte aligned: records move in dwords
+ * (16-byte aligned buffers, as gdsm_runs_alloc makes them, take the 16-byte loads).
+ * n == 0 writes rec_off[0] = 0 of every output and zero counts. The workspace is the context's and
+ * only grows. Not timed by a gdsm_prof_stage. */
+#define GDSM_SPLIT_DROP_EMPTY 1u
+int gdsm_runs_split(gdsm_ctx* ctx, const gdsm_runs* in, const uint32_t* ids,
+                    const uint32_t* dest, uint64_t per, uint32_t G, gdsm_runs* out,
+                    uint32_t* const* out_ids, uint64_t* counts, uint32_t flags);
+/* The same result on caller-owned memory, asynchronous on `stream` with no host synchronisation.
+ * counts is a DEVICE array of 2G u64 and always holds the true values (0 when the input is
+ * refused). Writes are guarded on the device: out_rec_off[d][j] only for j <= out_n_caps[d],
+ * out_ids[d][j] for j < out_n_caps[d], data only below out_caps[d], in whole dwords. err (device
+ * word, NULL: not reported) is OR-ed with 16 for malformed offsets and with 8 for a destination out
+ * of range; in either case no output data is written. workspace: 8-byte aligned, at least
+ * gdsm_runs_split_workspace_bytes(n, G) device bytes, contents need not be kept; -EINVAL for one
+ * that is NULL, misaligned or short, and for NULL counts. */
+uint64_t gdsm_runs_split_workspace_bytes(uint64_t n, uint32_t G);
+int gdsm_runs_split_raw(const uint64_t* rec_off, const uint8_t* data, uint64_t cap,
+                        const uint32_t* ids, const uint32_t* dest, uint64_t per, uint64_t n,
+                        uint32_t G, uint64_t* const* out_rec_off, uint8_t* const* out_data,
+                        const uint64_t* out_caps, const uint64_t* out_n_caps,
+                        uint32_t* const* out_ids, uint64_t* counts, uint32_t* err,
+                        uint32_t flags, void* workspace, uint64_t workspace_bytes, void* stream);
+
 const char* gdsm_version(void);
 /* Process-wide knobs that choose a kernel variant or launch form, for measurement and tests (every
  * value produces the same results). Key, accepted values, (default):
