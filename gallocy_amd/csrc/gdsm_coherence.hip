@@ -75,7 +75,8 @@ __device__ __forceinline__ uint32_t wave_incl_compose_dpp(uint32_t v) {
   return v;
 }
 
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
+// (on lane shuffles; gdsm_common.h has wave_sum64 on DPP)
+__device__ __forceinline__ uint64_t wave_sum64_shfl(uint64_t v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
   return v;
@@ -641,7 +642,7 @@ __device__ __forceinline__ void coh_fold_wave(uint64_t* __restrict__ pt, uint64_
     if (lane == 2u * q + 1u) mine = s >> 16;
   }
   if (lane < 10) partial[b * 10 + lane] = mine;
-  if (kM == 0 && __ballot(bad != 0) && lane == 0) atomicOr(err, 2u);
+  if (kM == 0 && __ballot(bad != 0) && lane == 0) atomicOr(err, kErrEvents);
   COH_FSTAMP(4, __builtin_amdgcn_s_memtime());
 }
 
@@ -1156,7 +1157,7 @@ __device__ __forceinline__ void coh_stream_wave(uint64_t* __restrict__ pt, uint6
   } else if (lane < 10) {
     partial[b * 10 + lane] = mine;
   }
-  if (__ballot(bad != 0) && lane == 0) atomicOr(err, 2u);
+  if (__ballot(bad != 0) && lane == 0) atomicOr(err, kErrEvents);
   if (kWT) GDSM_SSTAMP(ch.round, b, 3);
 }
 
@@ -1470,7 +1471,7 @@ __global__ __launch_bounds__(kRLThreads) void rounds_fold_lds_kernel(
   }
   __syncthreads();
   for (uint32_t i = t; i < np; i += kRLThreads) pt[base + i] = spt[i];
-  if (__syncthreads_or(bad) && t == 0) atomicOr(err, 2u);  // (kErrEvents)
+  if (__syncthreads_or(bad) && t == 0) atomicOr(err, kErrEvents);
 }
 
 const void* rounds_fold_kernel_ptr(bool xcd) {
@@ -1541,7 +1542,7 @@ __global__ __launch_bounds__(256) void coh_reduce_kernel(const uint32_t* __restr
     for (int q = 0; q < 10; ++q) acc[q] += partial[b * 10 + q];
   }
 #pragma unroll
-  for (int q = 0; q < 10; ++q) acc[q] = wave_sum64(acc[q]);
+  for (int q = 0; q < 10; ++q) acc[q] = wave_sum64_shfl(acc[q]);
   if (lane == 0)
 #pragma unroll
     for (int q = 0; q < 10; ++q) red[wave][q] = acc[q];

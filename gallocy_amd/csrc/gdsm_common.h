@@ -120,6 +120,34 @@ __device__ __forceinline__ uint64_t wave_incl_sum64(uint64_t x) {
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return lane_bcast(wave_incl_sum(v), 63); }
 
+// Sum of a u64 over the 64 lanes (mod 2^64), in every lane: the steps of wave_incl_sum on both
+// halves of the value (a lane without a source adds 0), then lane 63's total.
+template <int kCtrl, int kRowMask = 0xF>
+__device__ __forceinline__ uint64_t dpp0_64(uint64_t v) {
+  return (uint64_t)dpp0<kCtrl, kRowMask>((uint32_t)v) |
+         ((uint64_t)dpp0<kCtrl, kRowMask>((uint32_t)(v >> 32)) << 32);
+}
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t x) {
+  x += dpp0_64<0x111>(x);
+  x += dpp0_64<0x112>(x);
+  x += dpp0_64<0x114>(x);
+  x += dpp0_64<0x118>(x);
+  x += dpp0_64<0x142, 0xA>(x);
+  x += dpp0_64<0x143, 0xC>(x);
+  return lane_bcast64(x, 63);
+}
+
+// Rank of this lane among the set lanes of a 64-lane mask: the set bits below the lane's own.
+__device__ __forceinline__ uint32_t ballot_rank(uint64_t mask) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
+                                   __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+// ... of the ballot of p, which is returned in `ballot` (its popcount is the wave's count).
+__device__ __forceinline__ uint32_t ballot_rank(bool p, uint64_t& ballot) {
+  ballot = __ballot(p);
+  return ballot_rank(ballot);
+}
+
 // Value of lane l-1 (lane 0 gets 0) / of lane l+1 (lane 63 gets 0).
 __device__ __forceinline__ uint32_t from_prev_lane(uint32_t v) { return dpp0<0x138>(v); }
 __device__ __forceinline__ uint32_t from_next_lane(uint32_t v) { return dpp0<0x130>(v); }

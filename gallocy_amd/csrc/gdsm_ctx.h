@@ -89,14 +89,9 @@ struct gdsm_ctx {
 namespace gdsm {
 namespace detail {
 
-// Bits of the device error word (gdsm_ctx::err).
-constexpr uint32_t kErrRecord = 1;       // malformed record (apply)
-constexpr uint32_t kErrEvents = 2;       // coherence batch not sorted / out of range
-constexpr uint32_t kErrNw = 4;           // GPU NW input out of range
-constexpr uint32_t kErrIds = 8;          // page id / index out of range
-constexpr uint32_t kErrStream = 16;      // exchanged stream with malformed offsets
-constexpr uint32_t kErrOverBudget = 32;  // fixed-budget exchanged stream over its budget
-static_assert(gdsm::kErrRoundsBarrier == 64, "gdsm_rounds: a barrier that never completed");
+// Bits of the device error word (gdsm_ctx::err): defined in gdsm_launch.h, where the kernels see them.
+using gdsm::kErrRecord, gdsm::kErrEvents, gdsm::kErrNw, gdsm::kErrIds, gdsm::kErrStream,
+    gdsm::kErrOverBudget;
 
 int map_err(hipError_t e);
 // ctx->stream is being recorded into a graph (gdsm_capture_* or a caller's own capture of it).

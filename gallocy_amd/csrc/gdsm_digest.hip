@@ -8,14 +8,15 @@
 // a MAC: the keys are public, two unrelated pages collide with probability about 2^-64, a chosen
 // pair can be made to collide.
 //
-// Shape, as the page moves of gdsm_fetch.hip: a wave per 4 KiB page, four 16-B loads per lane, all
-// in flight before the arithmetic. Lane l always holds the words 4 (l + 64 q) .. + 3, q = 0 .. 3,
+// Shape, as every page move (load_page, gdsm_list.h): a wave per 4 KiB page, four 16-B loads per
+// lane, all in flight before the arithmetic. Lane l always holds the words 4 (l + 64 q) .. + 3, q = 0 .. 3,
 // so its keys are lane constants: 32 of them (8 per q: row 1's keys are row 0's four words on),
 // computed once per wave and kept in registers over the wave's pages. Per page and lane that
 // leaves 16 multiply-adds 32 x 32 -> 64 and 32 adds; the two u64 are then summed over the wave on
 // DPP (no LDS) and lane 0 stores them.
 #include "gdsm_common.h"
 #include "gdsm_launch.h"
+#include "gdsm_list.h"
 
 namespace gdsm {
 
@@ -32,36 +33,6 @@ __device__ __forceinline__ void lane_keys(uint32_t lane, LaneKeys& K) {
 #pragma unroll
     for (uint32_t c = 0; c < 8; ++c)
       K.k[q][c] = (uint32_t)(mix64(4ull * (lane + 64 * q) + c + 1) >> 32);
-}
-
-template <int kCtrl, int kRowMask = 0xF>
-__device__ __forceinline__ uint64_t dpp0_64(uint64_t v) {
-  return (uint64_t)dpp0<kCtrl, kRowMask>((uint32_t)v) |
-         ((uint64_t)dpp0<kCtrl, kRowMask>((uint32_t)(v >> 32)) << 32);
-}
-// Sum of a u64 over the 64 lanes (mod 2^64), in every lane: the steps of wave_incl_sum on both
-// halves of the value (a lane without a source adds 0), then lane 63's total.
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t x) {
-  x += dpp0_64<0x111>(x);
-  x += dpp0_64<0x112>(x);
-  x += dpp0_64<0x114>(x);
-  x += dpp0_64<0x118>(x);
-  x += dpp0_64<0x142, 0xA>(x);
-  x += dpp0_64<0x143, 0xC>(x);
-  return lane_bcast64(x, 63);
-}
-
-__device__ __forceinline__ void load_page(const uint8_t* __restrict__ src, uint32_t lane,
-                                          u32x4 (&v)[4]) {
-  const u32x4* s = reinterpret_cast<const u32x4*>(src);
-#pragma unroll
-  for (uint32_t q = 0; q < 4; ++q) v[q] = s[lane + 64 * q];
-}
-__device__ __forceinline__ void store_page(uint8_t* __restrict__ dst, uint32_t lane,
-                                           const u32x4 (&v)[4]) {
-  u32x4* d = reinterpret_cast<u32x4*>(dst);
-#pragma unroll
-  for (uint32_t q = 0; q < 4; ++q) d[lane + 64 * q] = v[q];
 }
 
 // (S0, S1) of the page held in v, in every lane.
@@ -112,7 +83,7 @@ __global__ __launch_bounds__(256) void digest_kernel(const uint8_t* __restrict__
       if (lane == 0) {
         out[2 * i] = 0;
         out[2 * i + 1] = 0;
-        if (err) atomicOr(err, 8u);
+        if (err) atomicOr(err, kErrIds);
       }
       continue;
     }
@@ -152,7 +123,7 @@ __global__ __launch_bounds__(256) void fetchc_offer_kernel(const uint8_t* __rest
       load_page(a + d * kPage, lane, v);
       digest_of(v, K, s0, s1);
     } else if (lane == 0) {
-      atomicOr(err, 8u);
+      atomicOr(err, kErrIds);
     }
     if (lane == 0) {
       dig[2 * k] = s0;
@@ -182,7 +153,7 @@ __global__ __launch_bounds__(256) void fetchc_verify_kernel(const uint8_t* __res
     if (p < base || p - base >= block) {  // wave-uniform
       if (lane == 0) {
         flags[j] = 0;
-        atomicOr(err, 8u);
+        atomicOr(err, kErrIds);
       }
       continue;
     }
@@ -209,9 +180,8 @@ __global__ __launch_bounds__(256) void fetchc_pos_kernel(const uint32_t* __restr
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   const bool set = i < m && flags[i] != 0;
-  const uint64_t B = __ballot(set);
-  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(B >> 32),
-                                                  __builtin_amdgcn_mbcnt_lo((uint32_t)B, 0u));
+  uint64_t B;
+  const uint32_t rank = ballot_rank(set, B);
   if (lane == 0) wcnt[wave] = (uint32_t)__popcll(B);
   __syncthreads();
   if (!kEmit) {
@@ -229,22 +199,9 @@ __global__ __launch_bounds__(256) void fetchc_scan_kernel(const uint32_t* __rest
                                                           uint64_t nblk,
                                                           uint32_t* __restrict__ blk_off,
                                                           uint32_t* __restrict__ total) {
-  __shared__ uint32_t wtot[4];
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t carry = 0;
-  for (uint64_t c0 = 0; c0 < nblk; c0 += 256) {
-    const uint64_t b = c0 + threadIdx.x;
-    const uint32_t v = b < nblk ? blk[b] : 0u;
-    const uint32_t inc = wave_incl_sum(v);
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    uint32_t pre = carry;
-    for (uint32_t w = 0; w < wave; ++w) pre += wtot[w];
-    if (b < nblk) blk_off[b] = pre + inc - v;
-    carry += wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = carry;
+  const uint32_t sum = block_excl_scan<uint32_t>(
+      nblk, [&](uint64_t b) { return blk[b]; }, [&](uint64_t b, uint32_t off) { blk_off[b] = off; });
+  if (threadIdx.x == 0) *total = sum;
 }
 
 // counts[p] = the changed pages of requester p's slice [off[p], off[p+1]) of the home's requests.
@@ -309,7 +266,7 @@ __global__ __launch_bounds__(256) void fetchc_place_kernel(const uint8_t* __rest
     const uint64_t p = pages[i];
     const uint64_t d = dst_ids ? dst_ids[i] : p;
     if (d >= n_pages || (kLocal && (p < base || p - base >= block))) {  // wave-uniform
-      if (lane == 0) atomicOr(err, 8u);
+      if (lane == 0) atomicOr(err, kErrIds);
       continue;
     }
     bool differs;
@@ -346,10 +303,7 @@ __global__ __launch_bounds__(256) void fetchc_place_kernel(const uint8_t* __rest
 // ------------------------------------------------------------------------- launchers
 // Memory-bound, a wave per page: at most 2048 workgroups (8 per CU), the rest by the waves'
 // stride, which also spreads a wave's key set-up over its pages.
-static inline unsigned page_grid(uint64_t pages) {
-  const uint64_t g = (pages + 3) / 4;
-  return g > 2048 ? 2048u : (g ? (unsigned)g : 1u);
-}
+static inline unsigned page_grid(uint64_t pages) { return grid_for(pages, 4, 2048); }
 
 hipError_t launch_digest(const uint8_t* arena, const uint32_t* ids, uint64_t n, uint64_t n_pages,
                          uint64_t* out, uint32_t* err, hipStream_t s, Prof* prof) {

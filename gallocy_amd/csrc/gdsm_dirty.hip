@@ -5,8 +5,9 @@
 // Three launches on the stream, ordered by their boundaries alone (no workgroup ever waits for
 // another):
 //   1. dirty_flag_kernel: the only one that touches the arenas. A workgroup takes a tile of 64
-//      consecutive list entries, each of its 4 waves 16 of them, a wave per page as the page moves
-//      of gdsm_fetch.hip: four 16-B loads per lane and arena. The next entry's eight loads are
+//      consecutive list entries, each of its 4 waves 16 of them, a wave per page in the layout of
+//      load_page (gdsm_list.h): four 16-B loads per lane and arena, the two arenas' interleaved
+//      (load_pair). The next entry's eight loads are
 //      issued before the current entry is reduced, so a wave always has loads in flight; there is
 //      no early exit inside a page (a clean page has to be read whole, and clean pages are the
 //      common case). Lane l holds the 16-B chunks l + 64 q: XOR / OR to one "differs" bit per
@@ -15,10 +16,12 @@
 //      pages' min(10244, 4 + 48 C).
 //   2. dirty_sum_kernel: one workgroup; exclusive scan of the tiles' dirty counts (the popcount
 //      of the flag word), the totals of counts and bounds into stats.
-//   3. dirty_emit_kernel: a wave per flag word, lane = entry; the rank inside the word is mbcnt.
+//   3. dirty_emit_kernel: a wave per flag word, lane = entry; its rank inside the word is
+//      ballot_rank of the word.
 // Flags, bounds and offsets are 32 B per 64 entries, next to the 512 KiB those entries read.
 #include "gdsm_common.h"
 #include "gdsm_launch.h"
+#include "gdsm_list.h"
 
 namespace gdsm {
 
@@ -53,23 +56,6 @@ __device__ __forceinline__ uint32_t chunks_differing(const Pair& v) {
     c += (uint32_t)__popcll(__ballot(((x.x | x.y) | (x.z | x.w)) != 0));
   }
   return c;
-}
-
-// Sum of a u64 over the 64 lanes, in every lane: wave_incl_sum's steps on a 64-bit value (both
-// halves moved, a lane without a source adds 0), then lane 63's total.
-template <int kCtrl, int kRowMask = 0xF>
-__device__ __forceinline__ uint64_t dpp0_64(uint64_t v) {
-  return (uint64_t)dpp0<kCtrl, kRowMask>((uint32_t)v) |
-         ((uint64_t)dpp0<kCtrl, kRowMask>((uint32_t)(v >> 32)) << 32);
-}
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t x) {
-  x += dpp0_64<0x111>(x);
-  x += dpp0_64<0x112>(x);
-  x += dpp0_64<0x114>(x);
-  x += dpp0_64<0x118>(x);
-  x += dpp0_64<0x142, 0xA>(x);
-  x += dpp0_64<0x143, 0xC>(x);
-  return lane_bcast64(x, 63);
 }
 
 }  // namespace
@@ -145,7 +131,7 @@ __global__ __launch_bounds__(256) void dirty_flag_kernel(const uint8_t* __restri
   if (lane == 0) {
     flags[slot] = (uint16_t)mask;
     bound[slot] = bnd;
-    if (n_bad && err) atomicOr(err, 8u);
+    if (n_bad && err) atomicOr(err, kErrIds);
   }
 }
 
@@ -156,26 +142,17 @@ __global__ __launch_bounds__(256) void dirty_sum_kernel(const uint64_t* __restri
                                                         const uint32_t* __restrict__ bound,
                                                         uint64_t T, uint64_t* __restrict__ off,
                                                         uint64_t* __restrict__ stats) {
-  __shared__ uint32_t wtot[4];
   __shared__ uint64_t wbnd[4];
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint64_t carry = 0, bsum = 0;
-  for (uint64_t c0 = 0; c0 < T; c0 += 256) {
-    const uint64_t t = c0 + threadIdx.x;
-    uint32_t v = 0;
-    if (t < T) {
-      v = (uint32_t)__popcll(flags[t]);
-      bsum += (uint64_t)bound[4 * t] + bound[4 * t + 1] + bound[4 * t + 2] + bound[4 * t + 3];
-    }
-    const uint32_t inc = wave_incl_sum(v);
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    uint64_t pre = carry;
-    for (uint32_t w = 0; w < wave; ++w) pre += wtot[w];
-    if (t < T) off[t] = pre + inc - v;
-    carry += (uint64_t)wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    __syncthreads();
-  }
+  uint64_t bsum = 0;
+  const uint64_t carry = block_excl_scan<uint64_t>(
+      T,
+      [&](uint64_t t) {
+        const uint32_t dirty = (uint32_t)__popcll(flags[t]);
+        bsum += (uint64_t)bound[4 * t] + bound[4 * t + 1] + bound[4 * t + 2] + bound[4 * t + 3];
+        return dirty;
+      },
+      [&](uint64_t t, uint64_t before) { off[t] = before; });
   bsum = wave_sum64(bsum);
   if (lane == 0) wbnd[wave] = bsum;
   __syncthreads();
@@ -201,9 +178,7 @@ __global__ __launch_bounds__(256) void dirty_emit_kernel(const uint64_t* __restr
   const uint64_t w = flags[t];
   if (w == 0) return;  // wave-uniform: most words of a sparse interval
   if (!((w >> lane) & 1ull)) return;
-  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(w >> 32),
-                                                  __builtin_amdgcn_mbcnt_lo((uint32_t)w, 0u));
-  const uint64_t k = off[t] + rank;
+  const uint64_t k = off[t] + ballot_rank(w);
   if (k >= cap) return;
   const uint64_t i = t * kTile + lane;
   if (pages_out) pages_out[k] = ids ? ids[i] : (uint32_t)i;

@@ -7,13 +7,15 @@
 // (gallocy/http/client.cpp:39-91); none of it is implemented there.
 //
 // Page moves are pure bandwidth (no arithmetic): a wave per 4 KiB page, four 16-B loads per lane,
-// all in flight before the stores, as twin_kernel (gdsm_pages.hip). Plain cached loads and stores:
+// all in flight before the stores (load_page / store_page, gdsm_list.h, which twin_kernel of
+// gdsm_pages.hip uses too). Plain cached loads and stores:
 // on this part nontemporal loads and/or stores measured 0.3-4.5 % slower for the same wave-per-page
 // copy (launch_twin), and an `nt` store keeps its line in L2 like a plain one
 // (MI355X_MICROARCH.md, stores of each flavour), so the hint buys nothing here. With both
 // destination arenas named the source is read once and stored twice.
 #include "gdsm_common.h"
 #include "gdsm_launch.h"
+#include "gdsm_list.h"
 
 namespace gdsm {
 
@@ -67,19 +69,6 @@ __global__ __launch_bounds__(256) void fetch_split_kernel(const uint32_t* __rest
 }
 
 // ------------------------------------------------------------------------- page moves
-__device__ __forceinline__ void load_page16(const uint8_t* __restrict__ src, uint32_t lane,
-                                            u32x4 (&v)[4]) {
-  const u32x4* s = reinterpret_cast<const u32x4*>(src);
-#pragma unroll
-  for (uint32_t q = 0; q < 4; ++q) v[q] = s[lane + 64 * q];
-}
-__device__ __forceinline__ void store_page16(uint8_t* __restrict__ dst, uint32_t lane,
-                                             const u32x4 (&v)[4]) {
-  u32x4* d = reinterpret_cast<u32x4*>(dst);
-#pragma unroll
-  for (uint32_t q = 0; q < 4; ++q) d[lane + 64 * q] = v[q];
-}
-
 // Home side: staging[j] := page req[j] - base of the home's source arena, for the n requests
 // received. An id outside the home's block [base, base + block) copies nothing and sets err bit 8
 // (the next gdsm_sync reports -EINVAL); it never addresses outside the arena.
@@ -94,12 +83,12 @@ __global__ __launch_bounds__(256) void fetch_gather_kernel(const uint8_t* __rest
        j += (uint64_t)gridDim.x * 4) {
     const uint64_t p = req[j];
     if (p < base || p - base >= block) {  // wave-uniform: one page per wave step
-      if (lane == 0) atomicOr(err, 8u);
+      if (lane == 0) atomicOr(err, kErrIds);
       continue;
     }
     u32x4 v[4];
-    load_page16(src + (p - base) * kPage, lane, v);
-    store_page16(staging + j * kPage, lane, v);
+    load_page(src + (p - base) * kPage, lane, v);
+    store_page(staging + j * kPage, lane, v);
   }
 }
 
@@ -129,13 +118,13 @@ __global__ __launch_bounds__(256) void fetch_place_kernel(const uint8_t* __restr
     const uint64_t p = pages[i];
     const uint64_t d = dst_ids ? dst_ids[i] : p;
     if (d >= n_pages || (kLocal && (p < base || p - base >= block))) {  // wave-uniform
-      if (lane == 0) atomicOr(err, 8u);
+      if (lane == 0) atomicOr(err, kErrIds);
       continue;
     }
     u32x4 v[4];
-    load_page16(from + (kLocal ? p - base : k) * kPage, lane, v);
-    store_page16(a0 + d * kPage, lane, v);
-    if (a1) store_page16(a1 + d * kPage, lane, v);
+    load_page(from + (kLocal ? p - base : k) * kPage, lane, v);
+    store_page(a0 + d * kPage, lane, v);
+    if (a1) store_page(a1 + d * kPage, lane, v);
   }
 }
 
@@ -162,9 +151,8 @@ __global__ __launch_bounds__(256) void fetch_list_kernel(const uint64_t* __restr
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   const uint64_t x = i < n ? notices[i] : 0;
   const bool keep = i < n && fetch_wanted(x, want);
-  const uint64_t B = __ballot(keep);
-  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(B >> 32),
-                                                  __builtin_amdgcn_mbcnt_lo((uint32_t)B, 0u));
+  uint64_t B;
+  const uint32_t rank = ballot_rank(keep, B);
   if (lane == 0) wcnt[wave] = (uint32_t)__popcll(B);
   __syncthreads();
   if (!kEmit) {
@@ -182,36 +170,17 @@ __global__ __launch_bounds__(256) void fetch_list_scan_kernel(const uint32_t* __
                                                               uint64_t nblk,
                                                               uint64_t* __restrict__ blk_off,
                                                               uint64_t* __restrict__ total) {
-  __shared__ uint32_t wtot[4];
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint64_t carry = 0;
-  for (uint64_t c0 = 0; c0 < nblk; c0 += 256) {
-    const uint64_t b = c0 + threadIdx.x;
-    const uint32_t v = b < nblk ? blk[b] : 0u;
-    const uint32_t inc = wave_incl_sum(v);
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    uint64_t pre = carry;
-    for (uint32_t w = 0; w < wave; ++w) pre += wtot[w];
-    if (b < nblk) blk_off[b] = pre + inc - v;
-    carry += (uint64_t)wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = carry;
+  const uint64_t sum = block_excl_scan<uint64_t>(
+      nblk, [&](uint64_t b) { return blk[b]; }, [&](uint64_t b, uint64_t off) { blk_off[b] = off; });
+  if (threadIdx.x == 0) *total = sum;
 }
 
 // ------------------------------------------------------------------------- launchers
-static inline unsigned grid_of(uint64_t work, unsigned per_block, unsigned cap) {
-  uint64_t g = (work + per_block - 1) / per_block;
-  if (g > cap) g = cap;
-  return g ? (unsigned)g : 1u;
-}
-
 hipError_t launch_fetch_split(const uint32_t* pages, const uint32_t* dst_ids, uint64_t n,
                               uint64_t total_pages, uint64_t per, uint32_t G, uint64_t n_pages,
                               uint64_t* counts, uint64_t* bounds, uint32_t* bad, hipStream_t s) {
   if (G > kFetchMaxRanks) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(fetch_split_kernel, dim3(grid_of(n, 256, 2048)), dim3(256), 0, s, pages,
+  hipLaunchKernelGGL(fetch_split_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, s, pages,
                      dst_ids, n, total_pages, per, G, n_pages, counts, bounds, bad);
   return hipGetLastError();
 }
@@ -219,7 +188,7 @@ hipError_t launch_fetch_split(const uint32_t* pages, const uint32_t* dst_ids, ui
 hipError_t launch_fetch_gather(const uint8_t* src, const uint32_t* req, uint64_t n, uint64_t base,
                                uint64_t block, uint8_t* staging, uint32_t* err, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(fetch_gather_kernel, dim3(grid_of(n, 4, 16384)), dim3(256), 0, s, src, req, n,
+  hipLaunchKernelGGL(fetch_gather_kernel, dim3(grid_for(n, 4, 16384)), dim3(256), 0, s, src, req, n,
                      base, block, staging, err);
   return hipGetLastError();
 }
@@ -229,7 +198,7 @@ hipError_t launch_fetch_scatter(const uint8_t* staging, const uint32_t* pages,
                                 uint64_t cnt, uint64_t n_pages, uint8_t* a0, uint8_t* a1,
                                 uint32_t* err, hipStream_t s) {
   if (cnt == 0) return hipSuccess;
-  hipLaunchKernelGGL(fetch_place_kernel<false>, dim3(grid_of(cnt, 4, 16384)), dim3(256), 0, s,
+  hipLaunchKernelGGL(fetch_place_kernel<false>, dim3(grid_for(cnt, 4, 16384)), dim3(256), 0, s,
                      staging, pages, dst_ids, 0ull, skip_at, skip, cnt, 0ull, 0ull, n_pages, a0, a1,
                      err);
   return hipGetLastError();
@@ -240,7 +209,7 @@ hipError_t launch_fetch_local(const uint8_t* src, const uint32_t* pages, const u
                               uint64_t n_pages, uint8_t* a0, uint8_t* a1, uint32_t* err,
                               hipStream_t s) {
   if (cnt == 0) return hipSuccess;
-  hipLaunchKernelGGL(fetch_place_kernel<true>, dim3(grid_of(cnt, 4, 16384)), dim3(256), 0, s, src,
+  hipLaunchKernelGGL(fetch_place_kernel<true>, dim3(grid_for(cnt, 4, 16384)), dim3(256), 0, s, src,
                      pages, dst_ids, first, 0ull, 0ull, cnt, base, block, n_pages, a0, a1, err);
   return hipGetLastError();
 }

@@ -31,6 +31,23 @@ int knob(Knob k);
 int tune(const char* key, int64_t value);
 constexpr uint32_t kSoloUnits = 16;  // pages of the one-workgroup release (gdsm_pages.hip, kSolo)
 
+// Bits of the device error word (gdsm_ctx::err), set by the kernels and read by gdsm_sync.
+constexpr uint32_t kErrRecord = 1;          // malformed record (apply, merge)
+constexpr uint32_t kErrEvents = 2;          // coherence batch not sorted / out of range
+constexpr uint32_t kErrNw = 4;              // GPU NW input out of range
+constexpr uint32_t kErrIds = 8;             // page id / index out of range
+constexpr uint32_t kErrStream = 16;         // stream with malformed offsets
+constexpr uint32_t kErrOverBudget = 32;     // fixed-budget exchanged stream over its budget
+constexpr uint32_t kErrRoundsBarrier = 64;  // gdsm_rounds: a persistent grid's barrier never completed
+constexpr uint32_t kErrRoundsWrites = 128;  // ... a round's writes not 8-B aligned or outside its pages
+
+// Workgroups of a launch: ceil(work / per_block), at most cap, at least 1.
+inline unsigned grid_for(uint64_t work, unsigned per_block, unsigned cap) {
+  uint64_t g = (work + per_block - 1) / per_block;
+  if (g > cap) g = cap;
+  return g ? (unsigned)g : 1u;
+}
+
 hipError_t launch_gen_pages(uint8_t* twin, uint8_t* cur, uint8_t* replica, uint64_t n,
                             uint64_t first_global, uint64_t stride, uint64_t seed, int mode,
                             uint32_t ppm, hipStream_t s);
@@ -46,10 +63,6 @@ hipError_t launch_twin(uint8_t* twin, const uint8_t* cur, const uint32_t* ids, u
 // Caller page-id lists checked by the diff launch itself (in the launch that zeroes its
 // workspace): safe_ids[i] = ids[i] if < n_pages, else n_pages (the guard page), the same for
 // tids, err |= 8 when any id was out of range. A null list is not checked.
-// Device error bit of a persistent grid's barrier that never completed (gdsm_rounds).
-constexpr uint32_t kErrRoundsBarrier = 64;
-// ... and of a round's writes that were not 8-B aligned or fell outside its released pages.
-constexpr uint32_t kErrRoundsWrites = 128;
 struct IdGuard {
   const uint32_t* ids;
   const uint32_t* tids;

@@ -24,6 +24,7 @@
 // over all lanes (publish_blocks), not over each lane's own positions.
 #include "gdsm_common.h"
 #include "gdsm_launch.h"
+#include "gdsm_list.h"
 #include "gdsm_record.h"
 
 namespace gdsm {
@@ -36,10 +37,6 @@ constexpr uint32_t kMergeMaxIn = 4u + 4u * kMaxRuns + kPage;
 // line, and one line of slack (a payload dword read at the record's end stays inside the buffer).
 constexpr uint32_t kMergeBufWords = (kMergeMaxIn + 12u + 15u) / 16u * 4u + 4u;
 constexpr uint32_t kTile = 4096;  // out pages per scan tile
-
-constexpr uint32_t kErrRecordBit = 1;   // gdsm_ctx::err bits (gdsm_ctx.h)
-constexpr uint32_t kErrIdsBit = 8;
-constexpr uint32_t kErrStreamBit = 16;
 
 struct WaveLds {
   uint32_t img[kPage / 4];    // the page image
@@ -176,28 +173,22 @@ __global__ __launch_bounds__(256) void merge_check_kernel(MergeIn in, const uint
     const uint64_t n = in.n[k];
     for (uint64_t i = t0; i <= n; i += st) {
       const uint64_t o = ro[i];
-      if ((o & 3u) || (i == 0 && o != 0)) v |= kErrStreamBit;
+      if ((o & 3u) || (i == 0 && o != 0)) v |= kErrStream;
       if (i < n) {
-        if (ro[i + 1] < o) v |= kErrStreamBit;
-        if (ids && i + 1 < n && ids[i + 1] <= ids[i]) v |= kErrIdsBit;
+        if (ro[i + 1] < o) v |= kErrStream;
+        if (ids && i + 1 < n && ids[i + 1] <= ids[i]) v |= kErrIds;
       } else if (o > in.cap[k]) {
-        v |= kErrStreamBit;
+        v |= kErrStream;
       }
     }
   }
   if (out_ids)
     for (uint64_t i = t0; i + 1 < n_out; i += st)
-      if (out_ids[i + 1] <= out_ids[i]) v |= kErrIdsBit;
-  const uint64_t any = __ballot(v != 0);
-  if (any) {
-    uint32_t w = v;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) w |= __shfl_xor(w, d, 64);
-    if ((threadIdx.x & 63) == (uint32_t)__builtin_ctzll(any)) {
-      atomicOr(fatal, 1u);
-      if (err) atomicOr(err, w);
-    }
-  }
+      if (out_ids[i + 1] <= out_ids[i]) v |= kErrIds;
+  wave_report(v, [&](uint32_t w) {
+    atomicOr(fatal, 1u);
+    if (err) atomicOr(err, w);
+  });
 }
 
 // ------------------------------------------------------------------------- sizes
@@ -233,7 +224,7 @@ __global__ __launch_bounds__(256) void merge_size_kernel(MergeIn in, const uint3
   const uint32_t size = cov_size(cov, nruns, pay);
   if (lane == 0) {
     sizes[i] = size;
-    if (any_bad && err) atomicOr(err, kErrRecordBit);
+    if (any_bad && err) atomicOr(err, kErrRecord);
   }
 }
 
@@ -483,7 +474,7 @@ __global__ __launch_bounds__(256) void merge_emit_kernel(
   uint32_t nruns, paybytes;
   const uint32_t size = cov_size(cov, nruns, paybytes);
   if (size != want) {  // the inputs changed between the launches: nothing is written
-    if (lane == 0 && err) atomicOr(err, kErrRecordBit);
+    if (lane == 0 && err) atomicOr(err, kErrRecord);
     return;
   }
   if (size == 0) return;

@@ -234,7 +234,7 @@ __global__ __launch_bounds__(64 * kWaves) void nw_fill_kernel(
   const uint64_t ao = a_off[pair], bo = b_off[pair];
   const uint64_t l1 = a_off[pair + 1] - ao, l2 = b_off[pair + 1] - bo;
   if (l1 > max_len || l2 > max_len) {
-    if (threadIdx.x == 0) atomicOr(err, 4u);
+    if (threadIdx.x == 0) atomicOr(err, kErrNw);
     return;
   }
   const uint32_t n1 = (uint32_t)l1, n2 = (uint32_t)l2;

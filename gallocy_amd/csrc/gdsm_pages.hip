@@ -13,6 +13,7 @@
 // No wave waits for a ticket that a wave not yet running holds.
 #include "gdsm_common.h"
 #include "gdsm_launch.h"
+#include "gdsm_list.h"
 #include "gdsm_record.h"
 
 namespace gdsm {
@@ -80,25 +81,13 @@ __global__ __launch_bounds__(256) void twin_kernel(uint8_t* __restrict__ twin,
       if (pg[k] == ~0ull) continue;
       if (pg[k] >= n_pages) {  // (wave-uniform: one page per wave step)
         pg[k] = n_pages;
-        if (err && lane == 0) atomicOr(err, 8u);
+        if (err && lane == 0) atomicOr(err, kErrIds);
       }
-      const u32x4* src = reinterpret_cast<const u32x4*>(cur + pg[k] * kPage);
-#pragma unroll
-      for (uint32_t q = 0; q < 4; ++q)
-        v[k][q] = (kNT & 1) ? __builtin_nontemporal_load(src + lane + 64 * q) : src[lane + 64 * q];
+      load_page<(kNT & 1) != 0>(cur + pg[k] * kPage, lane, v[k]);
     }
 #pragma unroll
-    for (uint32_t k = 0; k < kP; ++k) {
-      if (pg[k] == ~0ull) continue;
-      u32x4* dst = reinterpret_cast<u32x4*>(twin + pg[k] * kPage);
-#pragma unroll
-      for (uint32_t q = 0; q < 4; ++q) {
-        if (kNT & 2)
-          __builtin_nontemporal_store(v[k][q], dst + lane + 64 * q);
-        else
-          dst[lane + 64 * q] = v[k][q];
-      }
-    }
+    for (uint32_t k = 0; k < kP; ++k)
+      if (pg[k] != ~0ull) store_page<(kNT & 2) != 0>(twin + pg[k] * kPage, lane, v[k]);
   }
 }
 
@@ -143,7 +132,7 @@ __global__ __launch_bounds__(256) void check_ids_kernel(const uint32_t* __restri
     safe[i] = ok ? p : (uint32_t)n_pages;
     bad |= !ok;
   }
-  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(err, 8u);
+  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(err, kErrIds);
 }
 
 // Everything a diff launch needs zeroed or checked, as ONE launch before it (instead of a memset
@@ -170,7 +159,7 @@ __global__ __launch_bounds__(256) void diff_prep_kernel(uint64_t* __restrict__ z
       g.safe_tids[i] = p < g.n_pages ? p : (uint32_t)g.n_pages;
     }
   }
-  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(g.err, 8u);
+  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(g.err, kErrIds);
 }
 
 // ------------------------------------------------------------------------- exchanged streams
@@ -203,23 +192,17 @@ __global__ __launch_bounds__(256) void xchg_check_kernel(const uint64_t* __restr
       v |= 2u;
     }
   }
-  // one atomic per wave that found something
-  const uint64_t any = __ballot(v != 0);
-  if (any) {
-    uint32_t w = v;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) w |= __shfl_xor(w, d, 64);
-    if ((threadIdx.x & 63) == (uint32_t)__builtin_ctzll(any)) {
-      atomicOr(verdict, w);
-      atomicOr(err, ((w & 1u) ? 16u : 0u) | ((w & 2u) ? 32u : 0u) | ((w & 4u) ? 8u : 0u));
-    }
-  }
+  wave_report(v, [&](uint32_t w) {
+    atomicOr(verdict, w);
+    atomicOr(err, ((w & 1u) ? kErrStream : 0u) | ((w & 2u) ? kErrOverBudget : 0u) |
+                      ((w & 4u) ? kErrIds : 0u));
+  });
 }
 
 // The sender's view of a stream it shipped with a fixed budget: err |= 32 if it did not fit.
 __global__ void budget_check_kernel(const uint64_t* __restrict__ rec_off, uint64_t n,
                                     uint64_t budget, uint32_t* __restrict__ err) {
-  if (threadIdx.x == 0 && rec_off[n] > budget) atomicOr(err, 32u);
+  if (threadIdx.x == 0 && rec_off[n] > budget) atomicOr(err, kErrOverBudget);
 }
 
 __global__ __launch_bounds__(256) void xchg_zero_kernel(uint64_t* __restrict__ rec_off, uint64_t n,
@@ -628,9 +611,8 @@ __global__ __launch_bounds__(kSolo ? 64 * kSoloUnits : kChainW ? 64 * kChainW : 
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       m[k] = diffmask16(t[k], c[k]);
-      const uint64_t B = __ballot(m[k] != 0u);
-      const uint32_t rank = D + __builtin_amdgcn_mbcnt_hi(
-                                    (uint32_t)(B >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)B, 0u));
+      uint64_t B;
+      const uint32_t rank = D + ballot_rank(m[k] != 0u, B);
       if (m[k] && rank < 64u) {
         ent[rank] = ((uint32_t)(k * 64 + lane) << 16) | m[k];
         dat[rank] = c[k];
@@ -705,9 +687,9 @@ __global__ __launch_bounds__(kSolo ? 64 * kSoloUnits : kChainW ? 64 * kChainW : 
     if (lane == 0) solo_agg[wave] = agg;
     __syncthreads();
     for (uint32_t w = 0; w < wave; ++w) excl += solo_agg[w];
-    if (g.err && __ballot(bad_id != 0) && lane == 0) atomicOr(g.err, 8u);
+    if (g.err && __ballot(bad_id != 0) && lane == 0) atomicOr(g.err, kErrIds);
   }
-  if (kChain && g.err && __ballot(bad_id != 0) && lane == 0) atomicOr(g.err, 8u);
+  if (kChain && g.err && __ballot(bad_id != 0) && lane == 0) atomicOr(g.err, kErrIds);
   if (!kSolo && lane == 0)
     __hip_atomic_store(status + u, (u == u0 ? kStIncl : kStAgg) | tag | agg, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
@@ -968,7 +950,7 @@ __device__ __forceinline__ void release_page_wg(
   const uint32_t NR = all & 0xFFFFu, NP = all >> 16;
   const uint32_t size = NR ? 4u + 4u * NR + ((NP + 3u) & ~3u) : 0u;
   if (w == 0) {
-    if (g.err && __ballot(bad != 0) && lane == 0) atomicOr(g.err, 8u);
+    if (g.err && __ballot(bad != 0) && lane == 0) atomicOr(g.err, kErrIds);
     uint64_t* status = ws + 1;
     if (lane == 0)
       __hip_atomic_store(status + u, (u == 0 ? kStIncl : kStAgg) | tag | size, __ATOMIC_RELAXED,
@@ -1234,7 +1216,7 @@ __global__ __launch_bounds__(256) void apply_tiny_kernel(uint8_t* __restrict__ t
     ok = apply_rows<kMode, const uint32_t*, const uint8_t*, 64>(
         target + p * kPage, reinterpret_cast<const uint32_t*>(rec), rec, size, true, sink);
   }
-  if (__ballot(!ok) && lane == 0) atomicOr(err, 1u);
+  if (__ballot(!ok) && lane == 0) atomicOr(err, kErrRecord);
   if (kMode == 1 && sink == 0x9E3779B9u) atomicOr(err, 2u);
 }
 
@@ -1308,7 +1290,7 @@ __global__ __launch_bounds__(256) void apply_kernel(uint8_t* __restrict__ target
       j = k;
     }
   }
-  if (__ballot(bad != 0) && lane == 0) atomicOr(err, 1u);
+  if (__ballot(bad != 0) && lane == 0) atomicOr(err, kErrRecord);
   if (kMode == 1 && sink == 0x9E3779B9u) atomicOr(err, 2u);
 }
 
@@ -1618,7 +1600,7 @@ __global__ __launch_bounds__(256) void apply_flat_kernel(uint8_t* __restrict__ t
       j = k;
     }
   }
-  if (__ballot(bad != 0) && lane == 0) atomicOr(err, 1u);
+  if (__ballot(bad != 0) && lane == 0) atomicOr(err, kErrRecord);
   (void)sink;  // apply_rows<0> leaves it alone (measurement builds only)
 }
 
@@ -1714,13 +1696,6 @@ uint64_t diff_workspace_bytes(uint64_t n) {
   const uint64_t u1 = diff_variant() == 8 ? n : min(n, kDiffTiny);  // 1-page units
   const uint64_t base = 8 * (1 + max(max(u16, u2), u1)) + 64;
   return up256(base) + up256(4 * (uint64_t)kSpillWGs) + spill_pool_bytes(n);
-}
-
-static inline unsigned grid_for(uint64_t work, unsigned per_block, unsigned cap) {
-  uint64_t g = (work + per_block - 1) / per_block;
-  if (g > cap) g = cap;
-  if (g == 0) g = 1;
-  return (unsigned)g;
 }
 
 hipError_t launch_gen_pages(uint8_t* twin, uint8_t* cur, uint8_t* replica, uint64_t n,

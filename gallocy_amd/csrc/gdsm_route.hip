@@ -9,10 +9,11 @@
 //
 // Integer / index work, HBM-bound and tiny next to the fold itself: binary searches over sorted
 // event lists (split, merge by rank), one gather of the touched pages' words before the fold and
-// one after, and a per-destination compaction of the notices (ballot + mbcnt ranks inside a
-// block, one scan of the block counts).
+// one after, and a per-destination compaction of the notices (ballot_rank inside a block, one
+// block_excl_scan of the block counts per destination).
 #include "gdsm_common.h"
 #include "gdsm_launch.h"
+#include "gdsm_list.h"
 
 namespace gdsm {
 
@@ -171,9 +172,8 @@ __global__ __launch_bounds__(256) void notice_kernel(const uint64_t* __restrict_
   uint32_t rank[GDSM_MAX_NODES];
 #pragma unroll
   for (uint32_t d = 0; d < GDSM_MAX_NODES; ++d) {
-    const uint64_t B = __ballot((mask >> d) & 1u);
-    rank[d] = __builtin_amdgcn_mbcnt_hi((uint32_t)(B >> 32),
-                                        __builtin_amdgcn_mbcnt_lo((uint32_t)B, 0u));
+    uint64_t B;
+    rank[d] = ballot_rank((mask >> d) & 1u, B);
     if (lane == 0) wcnt[wave][d] = (uint32_t)__popcll(B);
   }
   __syncthreads();
@@ -200,24 +200,12 @@ __global__ __launch_bounds__(256) void notice_scan_kernel(const uint32_t* __rest
                                                           uint64_t* __restrict__ blk_off,
                                                           uint64_t* __restrict__ dest_total,
                                                           uint64_t* __restrict__ dest_base) {
-  __shared__ uint32_t wtot[4];
   __shared__ uint64_t tot[GDSM_MAX_NODES];
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (uint32_t d = 0; d < GDSM_MAX_NODES; ++d) {
-    uint64_t carry = 0;
-    for (uint64_t c0 = 0; c0 < nblk; c0 += 256) {
-      const uint64_t b = c0 + threadIdx.x;
-      const uint32_t v = b < nblk ? blk[b * GDSM_MAX_NODES + d] : 0u;
-      const uint32_t inc = wave_incl_sum(v);
-      if (lane == 63) wtot[wave] = inc;
-      __syncthreads();
-      uint64_t pre = carry;
-      for (uint32_t w = 0; w < wave; ++w) pre += wtot[w];
-      if (b < nblk) blk_off[b * GDSM_MAX_NODES + d] = pre + inc - v;
-      carry += (uint64_t)wtot[0] + wtot[1] + wtot[2] + wtot[3];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) tot[d] = d < G ? carry : 0;
+    const uint64_t sum = block_excl_scan<uint64_t>(
+        nblk, [&](uint64_t b) { return blk[b * GDSM_MAX_NODES + d]; },
+        [&](uint64_t b, uint64_t off) { blk_off[b * GDSM_MAX_NODES + d] = off; });
+    if (threadIdx.x == 0) tot[d] = d < G ? sum : 0;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -233,16 +221,10 @@ __global__ __launch_bounds__(256) void notice_scan_kernel(const uint32_t* __rest
 }
 
 // ------------------------------------------------------------------------- launchers
-static inline unsigned grid_of(uint64_t work, unsigned cap) {
-  uint64_t g = (work + 255) / 256;
-  if (g > cap) g = cap;
-  return g ? (unsigned)g : 1u;
-}
-
 hipError_t launch_route_split(const uint64_t* ev, uint64_t n, uint64_t total_pages, uint64_t per,
                               uint32_t G, uint64_t* counts, uint64_t* bounds, uint32_t* bad,
                               hipStream_t s) {
-  hipLaunchKernelGGL(route_split_kernel, dim3(grid_of(n, 2048)), dim3(256), 0, s, ev, n,
+  hipLaunchKernelGGL(route_split_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, s, ev, n,
                      total_pages, per, G, counts, bounds, bad);
   return hipGetLastError();
 }
@@ -252,8 +234,8 @@ hipError_t launch_route_merge(const uint64_t* runs, const uint64_t* off, uint32_
   RunOffsets o{};
   for (uint32_t t = 0; t <= G; ++t) o.o[t] = off[t];
   if (o.o[G] == 0) return hipSuccess;
-  hipLaunchKernelGGL(route_merge_kernel, dim3(grid_of(o.o[G], 8192)), dim3(256), 0, s, runs, o, G,
-                     base, out);
+  hipLaunchKernelGGL(route_merge_kernel, dim3(grid_for(o.o[G], 256, 8192)), dim3(256), 0, s, runs,
+                     o, G, base, out);
   return hipGetLastError();
 }
 
@@ -263,8 +245,8 @@ hipError_t launch_notice_pre(const uint64_t* pt, uint64_t n_pages, const uint64_
                              uint64_t n, uint32_t* pre, uint64_t* heads, hipStream_t s) {
   hipError_t e = hipMemsetAsync(heads, 0, 8, s);
   if (e != hipSuccess || n == 0) return e;
-  hipLaunchKernelGGL(notice_pre_kernel, dim3(grid_of(n, 8192)), dim3(256), 0, s, pt, n_pages, batch,
-                     n, pre, reinterpret_cast<unsigned long long*>(heads));
+  hipLaunchKernelGGL(notice_pre_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, pt, n_pages,
+                     batch, n, pre, reinterpret_cast<unsigned long long*>(heads));
   return hipGetLastError();
 }
 

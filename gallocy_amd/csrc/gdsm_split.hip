@@ -7,7 +7,8 @@
 // Five launches and one 4-B memset on one stream, ordered by their boundaries alone (no wave ever
 // waits for another, no host read in between):
 //   split_check_kernel  the input's offsets (from 0, non-decreasing, 4-aligned, inside the
-//                       capacity: merge_check_kernel's rules) before anything is read through them;
+//                       capacity: the rules merge_check_kernel applies) before anything is read
+//                       through them;
 //                       a failure sets the `fatal` word, which empties everything after it
 //   split_count_kernel  a workgroup per tile of 256 records, a thread per record: the record's
 //                       destinations (a bit >= G or a home >= G is fatal too) and size, reduced to
@@ -37,6 +38,7 @@
 //                       two edges of a span's range in a destination, and at a capacity.
 #include "gdsm_common.h"
 #include "gdsm_launch.h"
+#include "gdsm_list.h"
 
 namespace gdsm {
 
@@ -46,9 +48,6 @@ constexpr uint32_t kTile = kSplitTile;  // records per tile = threads of a workg
 constexpr uint32_t kSpan = 16384;       // input bytes per work item of the copy
 constexpr uint32_t kMaxG = 8;
 constexpr uint32_t kScanPer = 4;        // tiles per lane and step of the scan of the tile sums
-
-constexpr uint32_t kErrIdsBit = 8;  // gdsm_ctx::err bits (gdsm_ctx.h)
-constexpr uint32_t kErrStreamBit = 16;
 
 // The destinations of record i as a mask (bit d = out[d]) and the page id written for it. A mask
 // with a bit >= G or a home >= G returns bad (the caller makes it fatal).
@@ -91,11 +90,10 @@ __global__ __launch_bounds__(256) void split_check_kernel(const uint64_t* __rest
       v = 1;
     }
   }
-  const uint64_t any = __ballot(v != 0);
-  if (any && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(any)) {
+  wave_report(v, [&](uint32_t) {
     atomicOr(fatal, 1u);
-    if (err) atomicOr(err, kErrStreamBit);
-  }
+    if (err) atomicOr(err, kErrStream);
+  });
 }
 
 // ------------------------------------------------------------------------- tile sums
@@ -116,7 +114,7 @@ __global__ __launch_bounds__(256) void split_count_kernel(SplitArgs a, uint64_t*
   const uint64_t bad = __ballot(ds.bad);
   if (bad && lane == (uint32_t)__builtin_ctzll(bad)) {
     atomicOr(fatal, 1u);
-    if (err) atomicOr(err, kErrIdsBit);
+    if (err) atomicOr(err, kErrIds);
   }
   for (uint32_t d = 0; d < a.G; ++d) {
     const bool sel = (ds.mask >> d) & 1u;
@@ -201,9 +199,8 @@ __global__ __launch_bounds__(256) void split_index_kernel(SplitArgs a,
   for (uint32_t d = 0; d < kMaxG; ++d) {
     if (d >= a.G) break;
     const bool sel = (ds.mask >> d) & 1u;
-    const uint64_t bal = __ballot(sel);
-    rank[d] = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
-                                        __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+    uint64_t bal;
+    rank[d] = ballot_rank(sel, bal);
     const uint64_t v = sel ? size : 0ull;
     const uint64_t inc = wave_incl_sum64(v);
     pre[d] = inc - v;
@@ -231,7 +228,8 @@ __global__ __launch_bounds__(256) void split_index_kernel(SplitArgs a,
 
 // ------------------------------------------------------------------------- copy
 // The last record r <= n - 1 with ro[r] <= x (ro[0] = 0 <= x < ro[n]): the record holding input
-// byte x. The wave probes 64 points a step, as gdsm_merge's find_id.
+// byte x. The wave probes 64 points a step, as find_id of gdsm_merge.hip does for its lower bound
+// with an equality test; this is an upper bound over offsets, so the two stay apart.
 __device__ __forceinline__ uint64_t find_record(const uint64_t* __restrict__ ro, uint64_t n,
                                                 uint64_t x) {
   const uint32_t lane = lane_id();

@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void b64_decode_kernel(const uint8_t* __restri
     bytes[3 * q + 1] = (v >> 8) & 0xFFu;
     bytes[3 * q + 2] = v & 0xFFu;
   }
-  if (bad) atomicOr(err, 8u);
+  if (bad) atomicOr(err, kErrIds);
   if (ob + 12 <= F) {
     uint32_t* fw = reinterpret_cast<uint32_t*>(frame + ob);
 #pragma unroll
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void wire_check_kernel(const uint32_t* __restr
   if (i == 0) bad |= o != 0;
   if (i == n) bad |= o != D;
   else bad |= rec_off[i + 1] < o || ids[i] >= n_pages;
-  if (bad) atomicOr(err, 16u);
+  if (bad) atomicOr(err, kErrStream);
 }
 
 __global__ __launch_bounds__(256) void iota_kernel(uint32_t* __restrict__ dst, uint64_t n) {
@@ -137,10 +137,7 @@ __global__ __launch_bounds__(256) void iota_kernel(uint32_t* __restrict__ dst, u
     dst[i] = (uint32_t)i;
 }
 
-uint32_t grid(uint64_t threads) {
-  const uint64_t b = (threads + 255) / 256;
-  return (uint32_t)(b ? (b < (1u << 30) ? b : (1u << 30)) : 1);
-}
+constexpr unsigned kMaxGrid = 1u << 30;  // of the launches that take one item per thread
 
 }  // namespace
 
@@ -152,37 +149,35 @@ hipError_t launch_wire_sum(const uint8_t* frame, uint64_t F, uint64_t* sum, hipS
   hipError_t e = hipMemsetAsync(sum, 0, 8, s);
   if (e != hipSuccess) return e;
   const uint64_t nw = F / 8;
-  const uint32_t blocks = grid(nw) < 4096 ? grid(nw) : 4096;
-  hipLaunchKernelGGL(wire_sum_kernel, dim3(blocks), dim3(256), 0, s,
+  hipLaunchKernelGGL(wire_sum_kernel, dim3(grid_for(nw, 256, 4096)), dim3(256), 0, s,
                      reinterpret_cast<const uint64_t*>(frame), nw, sum);
   return hipGetLastError();
 }
 
 hipError_t launch_iota(uint32_t* dst, uint64_t n, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  const uint32_t blocks = grid(n) < 4096 ? grid(n) : 4096;
-  hipLaunchKernelGGL(iota_kernel, dim3(blocks), dim3(256), 0, s, dst, n);
+  hipLaunchKernelGGL(iota_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, s, dst, n);
   return hipGetLastError();
 }
 
 hipError_t launch_b64_encode(const uint8_t* frame, uint64_t F, uint8_t* text, hipStream_t s) {
   const uint64_t T = 4 * ((F + 2) / 3);
-  hipLaunchKernelGGL(b64_encode_kernel, dim3(grid((T + 15) / 16)), dim3(256), 0, s, frame, F,
-                     text, T);
+  hipLaunchKernelGGL(b64_encode_kernel, dim3(grid_for((T + 15) / 16, 256, kMaxGrid)), dim3(256), 0,
+                     s, frame, F, text, T);
   return hipGetLastError();
 }
 
 hipError_t launch_b64_decode(const uint8_t* text, uint64_t T, uint32_t pad, uint8_t* frame,
                              uint64_t F, uint32_t* err, hipStream_t s) {
-  hipLaunchKernelGGL(b64_decode_kernel, dim3(grid((T + 15) / 16)), dim3(256), 0, s, text, T, pad,
-                     frame, F, err);
+  hipLaunchKernelGGL(b64_decode_kernel, dim3(grid_for((T + 15) / 16, 256, kMaxGrid)), dim3(256), 0,
+                     s, text, T, pad, frame, F, err);
   return hipGetLastError();
 }
 
 hipError_t launch_wire_check(const uint32_t* ids, const uint64_t* rec_off, uint64_t n,
                              uint64_t D, uint64_t n_pages, uint32_t* err, hipStream_t s) {
-  hipLaunchKernelGGL(wire_check_kernel, dim3(grid(n + 1)), dim3(256), 0, s, ids, rec_off, n, D,
-                     n_pages, err);
+  hipLaunchKernelGGL(wire_check_kernel, dim3(grid_for(n + 1, 256, kMaxGrid)), dim3(256), 0, s, ids,
+                     rec_off, n, D, n_pages, err);
   return hipGetLastError();
 }
 

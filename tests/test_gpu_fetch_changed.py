@@ -53,17 +53,17 @@ def assert_digests_decide(grp, reqs, dsts, names):
     for mine, home, _ in dm.pairs(rep, reqs, dsts, [{a: h[a] for a in names} for h in grp.host],
                                   grp.Z):
         same_bytes = (mine == home).all(axis=1)
-        same_digest = (dm.digests(mine) == dm.digests(home)).all(axis=1)
-        assert np.array_equal(same_bytes, same_digest)
+        assert np.array_equal(same_bytes, ~dm.digests_differ(mine, home))
 
 
 def call_and_check(grp, reqs, dsts, names, outputs=True, tag=None):
     """One collective gdsm_fetch_changed; compares arenas, changed and stats with the model, updates
-    the host mirror and returns the stats per rank."""
+    the host mirror and returns the stats per rank (the model's changed flags: grp.want_changed)."""
     G, Z = grp.G, grp.Z
     rep = [h["replica"] for h in grp.host]
     want, want_ch, want_st = dm.fetch_changed(rep, reqs, dsts,
                                               [{a: h[a] for a in names} for h in grp.host], Z)
+    grp.want_changed = want_ch
     got_ch, got_st = [None] * G, [None] * G
 
     def rank(r):
@@ -93,12 +93,62 @@ def call_and_check(grp, reqs, dsts, names, outputs=True, tag=None):
     return want_st
 
 
-@pytest.mark.parametrize("G,Z", [(1, 37), (2, 130), (3, 1025), (4, 777), (8, 1031), (8, 5)])
+class BlockGroup(Group):
+    """As Group for 2 ranks and Z global pages, with contexts of one home block (Z / 2 pages) each
+    and every arena derived from one random block (a constant XORed in per rank and arena), which
+    keeps a list of more than 65536 pages affordable."""
+
+    def __init__(self, Z, seed):
+        rng = np.random.default_rng(seed)
+        per = fm.per_of(Z, 2)
+        self.G, self.Z = 2, Z
+        self.ctxs = [ga.Context(per) for _ in range(2)]
+        block = rng.integers(0, 2 ** 64, (per, 512), dtype=np.uint64).view(np.uint8)
+        self.host = []
+        for r, c in enumerate(self.ctxs):
+            h = {a: block ^ np.uint8(1 + 3 * r + i) for i, a in enumerate(ARENAS)}
+            for a in ARENAS:
+                c.upload(a, h[a])
+            self.host.append(h)
+        self.comms = exchange.Comm.loopback(self.ctxs)
+
+
+def scan_carry_case(Z):
+    """One call in which rank 0 requests every page homed at rank 1, more than 65536 of them, so
+    that the positions of the changed pages (fetchc_pos: 256 flags a block, one workgroup scanning
+    256 block counts a step) are scanned past the first step at the requester (its entries homed
+    elsewhere) and at the home (the requests it received), with changed pages on both sides of
+    entry 65536. Rank 1 requests a few pages of both homes. About one destination in fifteen
+    differs from the home copy."""
+    per = fm.per_of(Z, 2)
+    rng = np.random.default_rng(Z)
+    grp = BlockGroup(Z, seed=Z + 1)
+    try:
+        reqs = [np.arange(per, Z, dtype=np.uint32), np.array([0, 5, per, per + 1, Z - 1], np.uint32)]
+        dsts = [rng.permutation(per)[:len(q)].astype(np.uint32) for q in reqs]
+        names = ("current", "twin")
+        for r in range(2):
+            assert fm.valid_request(reqs[r], dsts[r], Z, per)
+        prepare(grp, rng, reqs, dsts, names, kinds=(0, 2, 3) + (1,) * 27)
+        assert_digests_decide(grp, reqs, dsts, names)
+        call_and_check(grp, reqs, dsts, names)
+        remote = reqs[0] // per != 0
+        changed = grp.want_changed[0][remote]
+        assert len(changed) > 65536 and changed[:65536].any() and changed[65536:].any()
+    finally:
+        grp.close()
+
+
+@pytest.mark.parametrize("G,Z", [(1, 37), (2, 130), (3, 1025), (4, 777), (8, 1031), (8, 5),
+                                 (2, 2 * 66000)])
 def test_fetch_changed_equals_model(G, Z):
     """Five calls in a row on the same contexts with the rotating request roles of
     test_fetch_equals_model: dst_ids NULL / injective, both arenas / CURRENT only / TWIN only,
     changed and stats given / NULL. About a quarter of the destinations each: equal in A only,
-    equal in both arenas, one byte off, unrelated."""
+    equal in both arenas, one byte off, unrelated. The last case is scan_carry_case."""
+    if Z > 2 * 65536:
+        assert G == 2
+        return scan_carry_case(Z)
     rng = np.random.default_rng(100 * G + Z)
     grp = Group(G, Z, seed=G * 7919 + Z + 1)
     try:

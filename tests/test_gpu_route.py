@@ -67,9 +67,24 @@ class Shard:
                                 np.zeros(self.nh, np.uint32))
 
 
+def notice_indices(stamped, want, shard):
+    """A home's batch length, and for every notice about one of its pages the index in that batch
+    (the nodes' events of the shard's pages, by page and seq) of the event the notice belongs to:
+    the first one of its page."""
+    ev = np.sort(np.concatenate(stamped)) >> np.uint64(36)
+    noticed = np.concatenate(want) & np.uint64(0xFFFFFFFF)
+    lo, hi = np.uint64(shard.base), np.uint64(shard.base + shard.nh)
+    ev = ev[(ev >= lo) & (ev < hi)]
+    return len(ev), np.searchsorted(ev, noticed[(noticed >= lo) & (noticed < hi)])
+
+
 @pytest.mark.parametrize("G,Z,n,hot", [(2, 5000, 3000, 0), (3, 4099, 20000, 500), (4, 777, 4000, 0),
-                                       (8, 9001, 3000, 300), (8, 64, 2000, 0)])
+                                       (8, 9001, 3000, 300), (8, 64, 2000, 0),
+                                       (2, 40000, 70000, 0)])
 def test_route_notify_equal_sequential_fold(G, Z, n, hot):
+    """The last case takes the scan of the per-block notice counts (one workgroup, 256 blocks of
+    256 events a step) past its first step: a home's batch of more than 65536 events, with notices
+    for events on both sides of index 65536."""
     rng = np.random.default_rng(G * 1000 + Z)
     shards = [Shard(r, G, Z) for r in range(G)]
     comms = exchange.Comm.loopback([s.ctx for s in shards])
@@ -82,6 +97,9 @@ def test_route_notify_equal_sequential_fold(G, Z, n, hot):
                 stamped[1] = stamped[1][:0]
             rc_ref, tot_ref, want = oracle.route_round(gst, gfl, stamped, G, Z)
             assert rc_ref == 0
+            if n > 65536 and batch == 0:
+                length, at = notice_indices(stamped, want, shards[0])
+                assert length > 65536 and (at < 65536).any() and (at >= 65536).any()
             got, tots, nb = [None] * G, [None] * G, [None] * G
 
             def rank(r):
