@@ -504,6 +504,8 @@ int gdsm_debug_fail_alloc(gdsm_ctx* ctx, int nth) {
   return 0;
 }
 
+int gdsm_debug_last_diff_variant(void) { return gdsm::last_diff_variant(); }
+
 int gdsm_prof_read(gdsm_ctx* ctx, double* ms, uint64_t* launches) {
   if (!ctx || !ms || !launches) return -EINVAL;
   CtxGuard g(ctx);

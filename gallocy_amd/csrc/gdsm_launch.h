@@ -83,6 +83,10 @@ struct DiffChain {
   uint32_t epoch = 0;  // the next launch's epoch, 1 .. 2^30 - 1; 0 = zero ws first
 };
 uint64_t diff_chain_bytes();
+// The geometry the calling thread's last diff launch took (gdsm_debug_last_diff_variant):
+// variant 1 .. 8 (gdsm_pages.hip's table) | form << 8; 0 before any launch on this thread.
+enum DiffForm { kFormGrid = 0, kFormSolo = 1, kFormChainPage = 2, kFormChainWave = 3 };
+int last_diff_variant();
 // With `guard`, the kernel reads guard->safe_ids / safe_tids in place of ids / tids.
 hipError_t launch_diff(const uint8_t* twin, const uint8_t* cur, const uint32_t* ids, uint64_t n,
                        uint64_t* rec_off, uint8_t* data, uint64_t cap, uint8_t* ws,

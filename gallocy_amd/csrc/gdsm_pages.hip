@@ -1946,6 +1946,10 @@ static hipError_t launch_diff_impl(const uint8_t* twin, const uint8_t* cur, cons
 
 uint64_t diff_chain_bytes() { return 8 * (1 + kDiffChainUnits); }
 
+// What launch_diff_impl last launched on this thread: variant | DiffForm << 8 (host side only).
+static thread_local int t_last_diff = 0;
+int last_diff_variant() { return t_last_diff; }
+
 hipError_t launch_diff(const uint8_t* twin, const uint8_t* cur, const uint32_t* ids, uint64_t n,
                        uint64_t* rec_off, uint8_t* data, uint64_t cap, uint8_t* ws,
                        uint64_t ws_bytes, hipStream_t s, Prof* prof, uint8_t* target,
@@ -2026,6 +2030,7 @@ static hipError_t launch_diff_impl(const uint8_t* twin, const uint8_t* cur, cons
   if (v == 8 && sp.G == 1 && nunits <= solo_max) {
     // one workgroup, no workspace: the caller's lists are guarded by the kernel itself
     const IdGuard g = guard ? *guard : IdGuard{};
+    t_last_diff = v | kFormSolo << 8;
     ProfScope ps(prof, GDSM_PROF_DIFF, s);
     auto kern = retwin ? (target ? diff_single_kernel<1, 4096, 4, true, 0, true, true>
                                  : diff_single_kernel<1, 4096, 4, false, 0, true, true>)
@@ -2046,6 +2051,8 @@ static hipError_t launch_diff_impl(const uint8_t* twin, const uint8_t* cur, cons
     const IdGuard g = guard ? *guard : IdGuard{};
     ProfScope ps(prof, GDSM_PROF_DIFF, s);
     const int cw = knob(kDiffChain);
+    t_last_diff = v | (cw == 3 || (cw == 2 && nunits <= kChainPerPage) ? kFormChainPage
+                                                                        : kFormChainWave) << 8;
     if (cw == 3 || (cw == 2 && nunits <= kChainPerPage)) {  // a page per four-wave workgroup
       auto kp = retwin ? (target ? release_page_kernel<true, true> : release_page_kernel<false, true>)
                        : (target ? release_page_kernel<true, false> : release_page_kernel<false, false>);
@@ -2108,6 +2115,7 @@ static hipError_t launch_diff_impl(const uint8_t* twin, const uint8_t* cur, cons
     if (e != hipSuccess) return e;
   }
   uint8_t* pool = spill ? ws + pool_at : nullptr;
+  t_last_diff = v | kFormGrid << 8;
   ProfScope ps(prof, GDSM_PROF_DIFF, s);
   auto kern = target ? (v == 5   ? diff_single_kernel<64, 8192, 4, true, kDiffSpill>
                        : v == 6 ? diff_single_kernel<32, 8192, 4, true, kDiffSpill>

@@ -738,6 +738,12 @@ int gdsm_tune(const char* key, int64_t value);
 /* Test hook: the nth next growth of one of ctx's internal workspaces fails with -ENOMEM (0 = off).
  * Used to show that a collective call refuses on every rank together when one rank fails. */
 int gdsm_debug_fail_alloc(gdsm_ctx* ctx, int nth);
+/* Test hook: the geometry the calling thread's last diff launch took (gdsm_diff, gdsm_diff_apply*,
+ * gdsm_release, gdsm_diff_split, gdsm_diff_raw, ...): variant | form << 8, the variant 1 .. 8 as
+ * the "diff_variant" key counts them (the one the automatic choice resolved to), the form 0 = the
+ * grid with its zeroing launch, 1 = one workgroup, 2 = chained, a page per workgroup, 3 = chained,
+ * a page per wave. 0 before any diff launch on this thread. */
+int gdsm_debug_last_diff_variant(void);
 
 #ifdef __cplusplus
 }  /* extern "C" */
