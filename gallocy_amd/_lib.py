@@ -140,6 +140,10 @@ SIGNATURES = {
     "gdsm_runs_split_raw": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_uint64,
                                       C.c_uint32, C.POINTER(vp), C.POINTER(vp), u64p, u64p,
                                       C.POINTER(vp), vp, vp, C.c_uint32, vp, C.c_uint64, vp]),
+    "gdsm_coh_retire": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
+                                  C.c_uint64, vp, C.c_uint64, vp, C.c_uint32]),
+    "gdsm_coh_select": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
+                                  vp, C.c_uint64, vp]),
     "gdsm_exchange": (C.c_int, [vp, vp, C.POINTER(GdsmRuns), C.POINTER(vp), C.POINTER(GdsmRuns),
                                 C.POINTER(vp), C.c_int, C.c_uint32]),
 }

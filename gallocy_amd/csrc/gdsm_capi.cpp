@@ -273,6 +273,7 @@ int gdsm_fini(gdsm_ctx* ctx) {
   if (ctx->fetch_ws) (void)hipFree(ctx->fetch_ws);
   if (ctx->dirty_ws) (void)hipFree(ctx->dirty_ws);
   if (ctx->split_ws) (void)hipFree(ctx->split_ws);
+  if (ctx->sweep_ws) (void)hipFree(ctx->sweep_ws);
   for (auto* p : ctx->ids_safe)
     if (p) (void)hipFree(p);
   for (auto& kv : ctx->runs_busy) (void)hipEventDestroy(kv.second);
@@ -1240,6 +1241,45 @@ int gdsm_coh_upload(gdsm_ctx* ctx, const uint32_t* state, const uint32_t* faults
     GDSM_TRY(hipMemcpy2DAsync(base + 1, 8, faults, 4, 4, ctx->n_pages, hipMemcpyHostToDevice,
                               ctx->stream));
   GDSM_TRY(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+// ---- page-table sweeps (SPEC §14) ---------------------------------------------------------
+// The refusals both sweeps share: no page table, a range outside the table or whose global pages
+// would reach bit 31's side of 2^28, a capacity with nowhere to write.
+static bool sweep_args_bad(const gdsm_ctx* ctx, uint64_t base, uint64_t first, uint64_t n,
+                           const uint32_t* out, uint64_t cap) {
+  if (!ctx || !ctx->coh_pt) return true;
+  if (first > ctx->n_pages || n > ctx->n_pages - first) return true;
+  if (base > GDSM_MAX_COH_PAGES || first + n > GDSM_MAX_COH_PAGES - base) return true;
+  return cap > 0 && !out;
+}
+
+int gdsm_coh_retire(gdsm_ctx* ctx, uint32_t node, uint32_t heir, uint64_t base, uint64_t per,
+                    uint64_t first, uint64_t n, uint32_t* moved_out, uint64_t cap, uint64_t* stats,
+                    uint32_t flags) {
+  if (sweep_args_bad(ctx, base, first, n, moved_out, cap)) return -EINVAL;
+  if (node >= ctx->n_nodes || heir >= ctx->n_nodes || heir == node || (flags & ~GDSM_RETIRE_DRY))
+    return -EINVAL;
+  CtxGuard g(ctx);
+  if (g.rc) return g.rc;
+  int rc = n ? ensure(ctx, &ctx->sweep_ws, &ctx->sweep_ws_bytes, gdsm::sweep_workspace_bytes(n)) : 0;
+  if (rc) return rc;
+  GDSM_TRY(gdsm::launch_coh_retire(ctx->coh_pt, ctx->n_nodes, node, heir, base, per, first, n,
+                                   moved_out, cap, stats, (flags & GDSM_RETIRE_DRY) != 0,
+                                   ctx->sweep_ws, ctx->sweep_ws_bytes, ctx->stream));
+  return 0;
+}
+
+int gdsm_coh_select(gdsm_ctx* ctx, uint32_t mask, uint32_t value, uint64_t base, uint64_t first,
+                    uint64_t n, uint32_t* pages_out, uint64_t cap, uint64_t* count) {
+  if (sweep_args_bad(ctx, base, first, n, pages_out, cap)) return -EINVAL;
+  CtxGuard g(ctx);
+  if (g.rc) return g.rc;
+  int rc = n ? ensure(ctx, &ctx->sweep_ws, &ctx->sweep_ws_bytes, gdsm::sweep_workspace_bytes(n)) : 0;
+  if (rc) return rc;
+  GDSM_TRY(gdsm::launch_coh_select(ctx->coh_pt, mask, value, base, first, n, pages_out, cap, count,
+                                   ctx->sweep_ws, ctx->sweep_ws_bytes, ctx->stream));
   return 0;
 }
 

@@ -71,6 +71,9 @@ struct gdsm_ctx {
   // gdsm_runs_split: the fatal word, the call's own error word, the counts and the tile sums
   uint8_t* split_ws = nullptr;
   uint64_t split_ws_bytes = 0;
+  // gdsm_coh_retire / gdsm_coh_select: wave counts, tile offsets and flag words
+  uint8_t* sweep_ws = nullptr;
+  uint64_t sweep_ws_bytes = 0;
   // checked copies of caller page-id lists (launch_check_ids): one per stream, so an async
   // apply's list is never overwritten by a call on the main stream
   // [2]: the target-page list of gdsm_diff_apply_ids (main stream, beside [0])

@@ -314,6 +314,24 @@ hipError_t launch_dirty_scan(const uint8_t* a, const uint8_t* b, const uint32_t*
                              uint64_t cap, uint64_t* stats, uint32_t* err, uint8_t* ws,
                              uint64_t ws_bytes, hipStream_t s);
 
+// Page-table sweeps (SPEC §14; gdsm_sweep.hip) over table pages [first, first + n) of pt (u64 =
+// state | faults << 32; first + n within the table, base + first + n <= 2^28). Retire: node out of
+// every copyset, the pages it owned to their heirs (per ? home : heir; a home >= n_nodes or == node
+// gives heir); stats (3 x u64, may be NULL) = {held, moved, orphaned}; moved_out[k] = (base + p) |
+// orphaned << 31 of the k-th moved page, ascending, the first cap of them; dry: the table is only
+// read. Select: pages_out[k] = base + p of the k-th page with (word & mask) == value, the first cap;
+// count (1 x u64, may be NULL). The counts are the true ones whatever cap is; a list may be NULL
+// (nothing emitted). ws: 16-byte aligned, sweep_workspace_bytes(n), its contents need not be kept.
+// Three launches on s (two without a list; n == 0: one memset), no host synchronisation.
+uint64_t sweep_workspace_bytes(uint64_t n);
+hipError_t launch_coh_retire(uint64_t* pt, uint32_t n_nodes, uint32_t node, uint32_t heir,
+                             uint64_t base, uint64_t per, uint64_t first, uint64_t n,
+                             uint32_t* moved_out, uint64_t cap, uint64_t* stats, bool dry,
+                             uint8_t* ws, uint64_t ws_bytes, hipStream_t s);
+hipError_t launch_coh_select(const uint64_t* pt, uint32_t mask, uint32_t value, uint64_t base,
+                             uint64_t first, uint64_t n, uint32_t* pages_out, uint64_t cap,
+                             uint64_t* count, uint8_t* ws, uint64_t ws_bytes, hipStream_t s);
+
 // Stream split (SPEC §13; gdsm_split.hip): the stream rec_off[n+1] / data[cap] partitioned stably
 // into G streams. dest (n masks, bit d = stream d) or, with dest NULL, the home ids[i] / per with
 // the page rewritten to ids[i] - home x per (ids NULL: page i); flags: GDSM_SPLIT_DROP_EMPTY. Every

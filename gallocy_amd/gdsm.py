@@ -22,6 +22,7 @@ TWIN, CURRENT, REPLICA = 0, 1, 2
 GEN_UNIFORM, GEN_CLUSTERED = 0, 1
 RELEASE_RETWIN = 1  # gdsm.h GDSM_RELEASE_RETWIN
 SPLIT_DROP_EMPTY = 1  # gdsm.h GDSM_SPLIT_DROP_EMPTY
+RETIRE_DRY = 1  # gdsm.h GDSM_RETIRE_DRY
 MAX_NODES = 8
 _ARENA = {"twin": TWIN, "current": CURRENT, "replica": REPLICA,
           TWIN: TWIN, CURRENT: CURRENT, REPLICA: REPLICA}
@@ -559,6 +560,65 @@ class Context:
         s = np.ascontiguousarray(state, np.uint32)
         f = np.ascontiguousarray(faults, np.uint32)
         check(lib().gdsm_coh_upload(self.handle, s.ctypes.data, f.ctypes.data), "gdsm_coh_upload")
+
+    def _sweep_list(self, out: Optional[DeviceBuffer], tot: DeviceBuffer, words: int, pick: int,
+                    cap: int):
+        """Synchronises; -> (the `words` totals, the first min(totals[pick], cap) list entries)."""
+        try:
+            self.sync()
+            t = [int(x) for x in tot.download(np.uint64, words)]
+            k = min(t[pick], cap)
+            lst = out.download(np.uint32, k) if k else np.zeros(0, np.uint32)
+        finally:
+            tot.free()
+            if out is not None:
+                out.free()
+        return t, lst
+
+    def coh_retire(self, node: int, heir: int, base: int = 0, per: int = 0, first: int = 0,
+                   n: Optional[int] = None, cap: Optional[int] = None, dry: bool = False) -> dict:
+        """gdsm_coh_retire (docs/SPEC.md §14): `node` leaves every copyset of table pages
+        [first, first + n) and the pages it owned go to their heirs (the §5 home (base + p) // per
+        where per > 0 and that home survives, else `heir`). dry: only count and list. cap: the
+        entries of the list (None: n; 0: counts only). Synchronises; -> {"held", "moved",
+        "orphaned", "pages" (the moved pages, base + p, ascending), "orphan_flags" (bool per listed
+        page)}."""
+        n = self.n_pages - first if n is None else int(n)
+        cap = n if cap is None else int(cap)
+        out = self.buffer(4 * cap) if cap else None
+        stats = self.buffer(24)
+        try:
+            check(lib().gdsm_coh_retire(self.handle, node, heir, base, per, first, n,
+                                        self._ptr(out), cap, stats.ptr, RETIRE_DRY if dry else 0),
+                  "gdsm_coh_retire")
+        except Exception:
+            stats.free()
+            if out is not None:
+                out.free()
+            raise
+        t, lst = self._sweep_list(out, stats, 3, 1, cap)
+        return {"held": t[0], "moved": t[1], "orphaned": t[2],
+                "pages": lst & np.uint32(0x7FFFFFFF), "orphan_flags": (lst >> np.uint32(31)) != 0}
+
+    def coh_select(self, mask: int, value: int, base: int = 0, first: int = 0,
+                   n: Optional[int] = None, cap: Optional[int] = None):
+        """gdsm_coh_select (docs/SPEC.md §14): the table pages p of [first, first + n) with
+        (word & mask) == value, as base + p, ascending. cap: the entries of the list (None: n; 0:
+        count only). Synchronises; -> (pages, count), count also where it exceeds cap."""
+        n = self.n_pages - first if n is None else int(n)
+        cap = n if cap is None else int(cap)
+        out = self.buffer(4 * cap) if cap else None
+        count = self.buffer(8)
+        try:
+            check(lib().gdsm_coh_select(self.handle, mask, value, base, first, n, self._ptr(out),
+                                        cap, count.ptr), "gdsm_coh_select")
+        except Exception:
+            count.free()
+            if out is not None:
+                out.free()
+            raise
+        t, lst = self._sweep_list(out, count, 1, 0, cap)
+        return lst, t[0]
 
     def gen_events(self, counts: np.ndarray, seed: int, n_nodes: int = 8, write_pct: int = 20,
                    first_page: int = 0) -> DeviceBuffer:

@@ -717,6 +717,56 @@ int gdsm_runs_split_raw(const uint64_t* rec_off, const uint8_t* data, uint64_t c
                         uint32_t* const* out_ids, uint64_t* counts, uint32_t* err,
                         uint32_t flags, void* workspace, uint64_t workspace_bytes, void* stream);
 
+/* ---- page-table sweeps: a node leaves; questions to the table (docs/SPEC.md §14) --------------
+ * Two passes over the page table of gdsm_coh_init that need no event batch and no download. Both
+ * work on table pages [first, first + n) and report page `base + p`, base = the shard's first
+ * global page as in gdsm_coherence_notify. The word layout is SPEC §5's (copyset bits 0-7, owner
+ * 8-15, state 16-17, dirty 18); `faults` is never touched.
+ *
+ * gdsm_coh_retire: node `node` leaves (a committed Raft configuration change). Per page p with word
+ * (c, o, s, d):
+ *   s == INVALID   unchanged, nothing counted;
+ *   c1 = c & ~bit(node); `held` counts the pages with c != c1;
+ *   o != node      the word becomes (c1, o, s, d): the state is kept (SHARED with only the owner
+ *                  left is legal; the §5 rules treat it conservatively);
+ *   o == node      the new owner is o' = heir(p): h = per ? (base + p) / per : heir, and h = heir
+ *                  when h >= n_nodes or h == node (§5's home where that home survives: a home
+ *                  always holds the home copy, which is why it may enter the copyset);
+ *                  c' = c1 | bit(o'), s' = EXCLUSIVE if c' == bit(o') else SHARED, d kept; `moved`
+ *                  counts it, and `orphaned` too when s == EXCLUSIVE and d is set: `node` held the
+ *                  only copy and had written it, so what it had not released is gone and the home
+ *                  copy is the newest that survives.
+ *   stats      device, 3 u64, may be NULL: {held, moved, orphaned};
+ *   moved_out  device, cap u32, may be NULL: (base + p) | orphaned << 31 per moved page, ascending.
+ * With GDSM_RETIRE_DRY the table is left as it is; stats and moved_out are what the wet call would
+ * give. Retiring is idempotent (a second call changes nothing and counts {0, 0, 0}), keeps
+ * "owner in copyset" and "EXCLUSIVE => copyset == {owner}" where they held, leaves `node` in no
+ * copyset and owning nothing, and is not a ban: later events of `node` are ordinary events, which
+ * is how a node rejoins.
+ *
+ * gdsm_coh_select: the pages p of the range with (word & mask) == value, as base + p, ascending,
+ * into pages_out (device, cap u32, may be NULL), and their number into count (device, 1 u64, may be
+ * NULL). mask 1 << d, value 1 << d: the pages node d holds, a valid list for gdsm_fetch.
+ *
+ * Capacity: the counts are always the true ones; only the first cap list entries are written and
+ * nothing at or past [cap]; a wet retire updates the whole range whatever cap is. A caller who
+ * cannot size cap = n runs GDSM_RETIRE_DRY (or a count-only select) first to learn the count.
+ * cap == 0 with a NULL list is the count-only form. n == 0 writes zero counts and nothing else.
+ * Asynchronous on the context's stream, after what was enqueued and after pending async applies;
+ * no host synchronisation: read stats / count after gdsm_sync. The workspace is the context's and
+ * only grows; a recording context that would have to grow it gets -EBUSY (sweep once before
+ * recording), otherwise the call can be recorded. Not timed by a gdsm_prof_stage.
+ * Immediate -EINVAL: NULL ctx; no page table (gdsm_coh_init not called); node or heir >= n_nodes;
+ * heir == node; unknown flags; first + n > gdsm_n_pages; base + first + n > GDSM_MAX_COH_PAGES (bit
+ * 31 stays free); cap > 0 with a NULL list. */
+#define GDSM_RETIRE_DRY 1u /* compute stats and moved_out, leave the table as it is */
+int gdsm_coh_retire(gdsm_ctx* ctx, uint32_t node, uint32_t heir, uint64_t base, uint64_t per,
+                    uint64_t first, uint64_t n, uint32_t* moved_out, uint64_t cap,
+                    uint64_t* stats /* device, 3 u64, may be NULL */, uint32_t flags);
+int gdsm_coh_select(gdsm_ctx* ctx, uint32_t mask, uint32_t value, uint64_t base,
+                    uint64_t first, uint64_t n, uint32_t* pages_out, uint64_t cap,
+                    uint64_t* count /* device, 1 u64, may be NULL */);
+
 const char* gdsm_version(void);
 /* Process-wide knobs that choose a kernel variant or launch form, for measurement and tests (every
  * value produces the same results). Key, accepted values, (default):
