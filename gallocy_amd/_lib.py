@@ -144,6 +144,8 @@ SIGNATURES = {
                                   C.c_uint64, vp, C.c_uint64, vp, C.c_uint32]),
     "gdsm_coh_select": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
                                   vp, C.c_uint64, vp]),
+    "gdsm_coh_clean": (C.c_int, [vp, C.c_uint32, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint32]),
+    "gdsm_coh_lookup": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp]),
     "gdsm_exchange": (C.c_int, [vp, vp, C.POINTER(GdsmRuns), C.POINTER(vp), C.POINTER(GdsmRuns),
                                 C.POINTER(vp), C.c_int, C.c_uint32]),
 }

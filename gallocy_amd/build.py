@@ -19,7 +19,7 @@ LIB = LIBDIR / "libgdsm.so"
 SOURCES = ["gdsm_pages.hip", "gdsm_coherence.hip", "gdsm_capi.cpp", "gdsm_tune.cpp", "legacy_diff.cpp",
            "gdsm_track.cpp", "gdsm_nw.hip", "gdsm_wire.hip", "gdsm_exchange.cpp", "gdsm_route.hip", "gdsm_probe.hip",
            "gdsm_merge.hip", "gdsm_fetch.hip", "gdsm_digest.hip", "gdsm_dirty.hip", "gdsm_split.hip",
-           "gdsm_sweep.hip"]
+           "gdsm_sweep.hip", "gdsm_cohlist.hip"]
 HEADERS = ["gdsm_common.h", "gdsm_launch.h", "gdsm_prof.h", "gdsm_track.h", "gdsm_ctx.h",
            "gdsm_record.h", "gdsm_list.h"]
 ARCH = os.environ.get("GDSM_ARCH", "gfx950")

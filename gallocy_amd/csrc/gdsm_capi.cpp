@@ -1283,6 +1283,36 @@ int gdsm_coh_select(gdsm_ctx* ctx, uint32_t mask, uint32_t value, uint64_t base,
   return 0;
 }
 
+// ---- the page table by page list (SPEC §15) -----------------------------------------------
+// The refusals both calls share: no page table, a list longer than 2^32 or, without ids, than the
+// table, any entry at all for a table of 0 pages, a base past the global pages.
+static bool cohlist_args_bad(const gdsm_ctx* ctx, const uint32_t* ids, uint64_t n, uint64_t base) {
+  if (!ctx || !ctx->coh_pt || (n && ctx->n_pages == 0)) return true;
+  if (n > (1ull << 32) || base > GDSM_MAX_COH_PAGES) return true;
+  return !ids && n > ctx->n_pages;
+}
+
+int gdsm_coh_clean(gdsm_ctx* ctx, uint32_t node, const uint32_t* ids, uint64_t n, uint64_t base,
+                   uint8_t* status_out, uint64_t* stats, uint32_t flags) {
+  if (cohlist_args_bad(ctx, ids, n, base) || node >= ctx->n_nodes || flags) return -EINVAL;
+  CtxGuard g(ctx);
+  if (g.rc) return g.rc;
+  GDSM_TRY(gdsm::launch_coh_clean(ctx->coh_pt, ctx->n_pages, node, ids, n, base, status_out, stats,
+                                  ctx->err, ctx->stream));
+  return 0;
+}
+
+int gdsm_coh_lookup(gdsm_ctx* ctx, const uint32_t* ids, uint64_t n, uint64_t base, uint32_t shift,
+                    uint32_t mask, uint32_t* out, uint32_t* faults_out) {
+  if (cohlist_args_bad(ctx, ids, n, base) || shift > 31 || (n && !out)) return -EINVAL;
+  if (n == 0) return 0;
+  CtxGuard g(ctx);
+  if (g.rc) return g.rc;
+  GDSM_TRY(gdsm::launch_coh_lookup(ctx->coh_pt, ctx->n_pages, ids, n, base, shift, mask, out,
+                                   faults_out, ctx->err, ctx->stream));
+  return 0;
+}
+
 int gdsm_gen_events(gdsm_ctx* ctx, uint64_t* events, const uint64_t* offsets, uint64_t first_page,
                     uint64_t n, uint64_t seed, uint32_t n_nodes, uint32_t write_pct) {
   if (!ctx || (n && (!events || !offsets)) || n_nodes == 0 || n_nodes > GDSM_MAX_NODES ||

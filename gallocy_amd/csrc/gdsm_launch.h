@@ -332,6 +332,24 @@ hipError_t launch_coh_select(const uint64_t* pt, uint32_t mask, uint32_t value, 
                              uint64_t first, uint64_t n, uint32_t* pages_out, uint64_t cap,
                              uint64_t* count, uint8_t* ws, uint64_t ws_bytes, hipStream_t s);
 
+// The page table by page list (SPEC §15; gdsm_cohlist.hip): entry i of the device list ids (n
+// entries, 4-B aligned; NULL: table pages 0 .. n-1, n <= n_pages) works on table page ids[i] - base
+// of pt (n_pages >= 1 u64 words). Clean: the dirty bit of the pages `node` owns dirty is cleared
+// with a 32-bit atomic on the state half; status_out (n bytes, may be NULL): 0 cleaned, 1 already
+// clean, 2 owned by another node, 3 INVALID, 4 out of range; stats (4 x u64, may be NULL; zeroed
+// by a memset node ahead of the launch) = {cleaned, already, stale, skipped (3 and 4)}. Lookup:
+// out[i] = INVALID or out of range ? 0 : (word >> shift) & mask; faults_out[i] (may be NULL) = the
+// page's faults, 0 out of range. An id out of range sets kErrIds in *err. One launch on s, no
+// workspace, no host synchronisation; n == 0: only the memset of stats. hipErrorInvalidValue, with
+// nothing enqueued: n > 2^32, n > 0 with n_pages == 0, ids NULL with n > n_pages, lookup's n > 0
+// with out NULL or shift > 31.
+hipError_t launch_coh_clean(uint64_t* pt, uint64_t n_pages, uint32_t node, const uint32_t* ids,
+                            uint64_t n, uint64_t base, uint8_t* status_out, uint64_t* stats,
+                            uint32_t* err, hipStream_t s);
+hipError_t launch_coh_lookup(const uint64_t* pt, uint64_t n_pages, const uint32_t* ids, uint64_t n,
+                             uint64_t base, uint32_t shift, uint32_t mask, uint32_t* out,
+                             uint32_t* faults_out, uint32_t* err, hipStream_t s);
+
 // Stream split (SPEC §13; gdsm_split.hip): the stream rec_off[n+1] / data[cap] partitioned stably
 // into G streams. dest (n masks, bit d = stream d) or, with dest NULL, the home ids[i] / per with
 // the page rewritten to ids[i] - home x per (ids NULL: page i); flags: GDSM_SPLIT_DROP_EMPTY. Every

@@ -620,6 +620,51 @@ class Context:
         t, lst = self._sweep_list(out, count, 1, 0, cap)
         return lst, t[0]
 
+    def coh_clean(self, node: int, ids=None, n: Optional[int] = None, base: int = 0,
+                  status: bool = False) -> dict:
+        """gdsm_coh_clean (docs/SPEC.md §15): clears the dirty bit of the table pages ids[i] - base
+        (`ids`: a DeviceBuffer or device pointer of global pages, repeats allowed; None = table
+        pages 0..n-1) that `node` owns dirty, as after a release of `node` that shipped them.
+        Synchronises; -> {"cleaned", "already", "stale", "skipped"}, with status=True also
+        "status" (uint8 per entry: 0 cleaned, 1 already clean, 2 owned by another node, 3 INVALID,
+        4 out of range)."""
+        n = self._count(ids, n)
+        d_status = self.buffer(max(n, 1)) if status else None
+        stats = self.buffer(32)
+        try:
+            check(lib().gdsm_coh_clean(self.handle, node, self._ptr(ids), n, base,
+                                       self._ptr(d_status), stats.ptr, 0), "gdsm_coh_clean")
+            self.sync()
+            t = [int(x) for x in stats.download(np.uint64, 4)]
+            r = dict(zip(("cleaned", "already", "stale", "skipped"), t))
+            if status:
+                r["status"] = d_status.download(np.uint8, n)
+        finally:
+            stats.free()
+            if d_status is not None:
+                d_status.free()
+        return r
+
+    def coh_lookup(self, ids=None, n: Optional[int] = None, base: int = 0, shift: int = 0,
+                   mask: int = 0xFFFFFFFF, faults: bool = False):
+        """gdsm_coh_lookup (docs/SPEC.md §15): per entry of `ids` (as in coh_clean) the field
+        (word >> shift) & mask of table page ids[i] - base, 0 where the page is INVALID or out of
+        range. shift 0 with mask 0xFF & ~bit(writer) & ~bit(home) is runs_split's `dest`.
+        Asynchronous, recordable; -> the DeviceBuffer of n uint32, or with faults=True the pair
+        (fields, the pages' faults). Read them with .download(np.uint32, n) after a sync."""
+        n = self._count(ids, n)
+        out = self.buffer(4 * max(n, 1))
+        fl = self.buffer(4 * max(n, 1)) if faults else None
+        try:
+            check(lib().gdsm_coh_lookup(self.handle, self._ptr(ids), n, base, shift, mask, out.ptr,
+                                        self._ptr(fl)), "gdsm_coh_lookup")
+        except Exception:
+            out.free()
+            if fl is not None:
+                fl.free()
+            raise
+        return (out, fl) if faults else out
+
     def gen_events(self, counts: np.ndarray, seed: int, n_nodes: int = 8, write_pct: int = 20,
                    first_page: int = 0) -> DeviceBuffer:
         counts = np.ascontiguousarray(counts, dtype=np.uint64)

@@ -767,6 +767,56 @@ int gdsm_coh_select(gdsm_ctx* ctx, uint32_t mask, uint32_t value, uint64_t base,
                     uint64_t first, uint64_t n, uint32_t* pages_out, uint64_t cap,
                     uint64_t* count /* device, 1 u64, may be NULL */);
 
+/* ---- the page table by page list: clean after a release, look fields up (docs/SPEC.md §15) ----
+ * Where the sweeps take a range of the table, these two take a device list of page ids, the form
+ * every other call speaks in (gdsm_release, gdsm_dirty_scan, gdsm_exchange's send_ids / recv_ids,
+ * gdsm_fetch). ids[i] is a GLOBAL page; entry i works on table page p = ids[i] - base, base = the
+ * shard's first global page as in the sweeps (0 for recv_ids / send_ids, which are local). ids ==
+ * NULL means table pages 0 .. n-1. The list needs no order, only 4-byte alignment, and may repeat
+ * pages. The word layout is SPEC §5's; bits 19-31 of a word and `faults` are never written.
+ *
+ * gdsm_coh_clean: a release of `node` reached the home, so the dirty bit of the pages it shipped is
+ * cleared. Per entry, with word (c, o, s, d) of page p:
+ *   status 0 CLEANED  s != INVALID, o == node, d == 1: d := 0, nothing else in the word changes
+ *                     (state and copyset kept);                                   stats[0]
+ *   status 1 ALREADY  s != INVALID, o == node, d == 0: no effect;                 stats[1]
+ *   status 2 STALE    s != INVALID, o != node: no effect (somebody wrote the page after `node`
+ *                     did; that writer's own release will clean it);              stats[2]
+ *   status 3 SKIPPED  s == INVALID: no effect;                                    stats[3]
+ *   status 4 SKIPPED  ids[i] < base or p >= gdsm_n_pages: no effect, and the next gdsm_sync
+ *                     reports -EINVAL (as gdsm_digest does for such an id);       stats[3]
+ *   status_out  device, n bytes, may be NULL: the status of entry i;
+ *   stats       device, 4 u64, may be NULL: {cleaned, already, stale, skipped}; they sum to n. The
+ *               call zeroes and then counts them itself. n == 0 writes four zeros and nothing else.
+ * A page listed more than once is cleaned, and counted as cleaned, exactly once; its other entries
+ * report ALREADY, and which entry reports CLEANED is unspecified. The call is idempotent, keeps
+ * every invariant the sweeps keep, leaves a valid input of the SPEC §5 fold, and a later write
+ * event sets the bit again. After cleaning the list that gdsm_coh_select(owns dirty, d) returned,
+ * with node = d, that select returns nothing and gdsm_coh_retire(d) reports orphaned == 0.
+ *
+ * gdsm_coh_lookup: out[i] = (s == INVALID) ? 0 : (word >> shift) & mask, and, where faults_out is
+ * given, faults_out[i] = faults[p]. An id out of range gives 0 / 0 and the next gdsm_sync reports
+ * -EINVAL. shift 0, mask 0xFF & ~bit(writer) & ~bit(home): the `dest` array of gdsm_runs_split's
+ * mask form as it stands (the copyset of each record's page, without the two nodes that have the
+ * bytes already); shift 8, mask 0xFF: the owners; shift 0, mask ~0u: the words. The table is only
+ * read.
+ *
+ * Both are asynchronous on the context's stream, after what was enqueued and after pending async
+ * applies; no host synchronisation and no workspace, so both can always be recorded, and a replay
+ * reads the table and the list again. Read stats, status_out and out after gdsm_sync. Where the
+ * page table lives in a context of its own, synchronise the data context that produced the list
+ * (gdsm_sync, or an event the table's stream waits for) before the call: the two streams are not
+ * ordered otherwise. Not timed by a gdsm_prof_stage.
+ * Immediate -EINVAL: NULL ctx; no page table (gdsm_coh_init not called); node >= n_nodes; flags
+ * != 0; shift > 31; n > 2^32; base > GDSM_MAX_COH_PAGES; ids == NULL with n > gdsm_n_pages;
+ * n > 0 on a table of 0 pages; n > 0 with a NULL out (lookup). */
+int gdsm_coh_clean(gdsm_ctx* ctx, uint32_t node, const uint32_t* ids, uint64_t n, uint64_t base,
+                   uint8_t* status_out /* device, n bytes, may be NULL */,
+                   uint64_t* stats /* device, 4 u64, may be NULL */, uint32_t flags /* 0 */);
+int gdsm_coh_lookup(gdsm_ctx* ctx, const uint32_t* ids, uint64_t n, uint64_t base,
+                    uint32_t shift, uint32_t mask, uint32_t* out /* device, n u32 */,
+                    uint32_t* faults_out /* device, n u32, may be NULL */);
+
 const char* gdsm_version(void);
 /* Process-wide knobs that choose a kernel variant or launch form, for measurement and tests (every
  * value produces the same results). Key, accepted values, (default):
